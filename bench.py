@@ -20,7 +20,15 @@ Positives: the reference's own triples where the snapshot has th
 permutation, read sequentially), FB15k-237 / YAGO3-10 valid+test for C3 / C4; negatives
 RandomState(2).randint(E, (B, N)).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|...] [--dry-run]
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit,
+ms_per_step, ...). `--full` adds everything else the line can carry, each from runs of its own after the
+timed steps: the roofline object (per-mode and planned / unplanned step times, PMC traffic), the train
+step, the YAGO3-10 row-sharded sections and the CPU baseline (--train-steps, --sharded-steps and
+--no-cpu-baseline size or drop them). `--dump-outputs DIR` writes what the last timed step returned to its
+caller as DIR/<name>.npy: the inputs are seeded, so two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|...] [--full]
+                       [--dump-outputs DIR] [--dry-run]
 """
 from __future__ import annotations
 
@@ -213,6 +221,32 @@ def load_triples(w):
     return tri
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+STEP_OUTPUTS = ("out_neg", "out_pos", "neg_scores", "pos_scores")  # step_forward_raw / StepPlanner.step
+
+
+def dump_outputs(dirname, names, out):
+    """--dump-outputs: the tensors the last timed step returned (`out`: one tensor, or a tuple named by
+    `names`) as dirname/<name>.npy, float32 as computed (anything else as float64). Past DUMP_LIMIT_BYTES in
+    all, every array is cut to the same fraction of its elements: a sorted RandomState(0) sample of its
+    flattened form, the same elements on every run."""
+    if out is None:  # no timed step ran
+        return
+    outs = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+    arrays = []
+    for name, t in zip(names, outs):
+        x = t.detach().cpu().numpy()
+        arrays.append((name, x if x.dtype == np.float32 else x.astype(np.float64)))
+    total = sum(x.nbytes for _, x in arrays)
+    os.makedirs(dirname, exist_ok=True)
+    for name, x in arrays:
+        if total > DUMP_LIMIT_BYTES:
+            keep = x.size * DUMP_LIMIT_BYTES // total
+            x = x.reshape(-1)[np.sort(np.random.RandomState(0).choice(x.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), x)
+
+
 def positives(w, rank, n_batches, world=1):
     """[n_batches] x [B, 3] positives: the dataset's triples in a RandomState(0) permutation, read
     sequentially (rank r takes every world-th batch), or uniform random ids without a dataset."""
@@ -331,7 +365,7 @@ def _global_batches(w, world, n, device):
 def sharded_bench(w, a, world, rank, device, dist_on, train=False):
     """c4s: ShardedKGE.step_forward (or, with train, ShardedKGE.train_step: the whole row-sharded
     train step with Keras Adam) on the global batch; the timed step includes every collective.
-    Returns the elapsed seconds of a.steps steps (this rank)."""
+    Returns the elapsed seconds of a.steps steps (this rank) and what the last of them returned."""
     from customknowledgegraphembedding_amd.distributed import ShardedKGE
     sk = ShardedKGE(w["fn"], w["nentity"], w["nrelation"], w["hidden_dim"], w["gamma"],
                     double_entity_embedding=w["de"], double_relation_embedding=w["dr"],
@@ -381,12 +415,13 @@ def sharded_bench(w, a, world, rank, device, dist_on, train=False):
         tdist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(a.warmup, a.warmup + a.steps):
-        step(batches[i % 4], i)
+        last = step(batches[i % 4], i)
     torch.cuda.synchronize()
     if dist_on:
         tdist.barrier()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, last
 
 
 # The native executor's two forms measured at N > 1: the collectives on the step's own stream with
@@ -904,6 +939,8 @@ def eval_bench(w, a, device, world=1, rank=0, dist_on=False):
     flops = 2.0 * Bq * E * K            # the fp32 contraction
     kp = (K + 15) // 16 * 16
     mfma_flops = 6 * 2.0 * Bq * E * kp  # bf16 MFMA work executed (six products, K padded to 16)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, ("ranks",), ranks[-1] if ranks else None)
     r = torch.cat(ranks)
     if dist_on:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -951,8 +988,8 @@ def eval_bench(w, a, device, world=1, rank=0, dist_on=False):
 def transparse_bench(w, a, device):
     """c6: TranSparse scoring step = both calls of supervisor.py:17-18 in kge_transparse_step_forward (head-batch
     negatives [B, N] on the bf16x3 MFMA forms with their row reduction, the positives [B, 1] with their
-    logsigmoid; events around the call), after the mask product (kge_transparse_premul); plus the autograd train
-    step (deterministic backward + HIP Adam) as a side measurement."""
+    logsigmoid; events around the call), after the mask product (kge_transparse_premul); plus, with --full, the
+    autograd train step (deterministic backward + HIP Adam) as a side measurement."""
     from customknowledgegraphembedding_amd.model import TFKGEModel
     from customknowledgegraphembedding_amd.optim import Adam
     from customknowledgegraphembedding_amd.supervisor import Strategy, Sum, Trainer
@@ -983,10 +1020,13 @@ def transparse_bench(w, a, device):
     torch.cuda.synchronize()
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
     t0 = time.perf_counter()
+    last = None
     for i in range(a.steps):
-        step(batches[i % 4], evs[i])
+        last = step(batches[i % 4], evs[i])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, STEP_OUTPUTS[:2], last)
     k_s = statistics.mean(e0.elapsed_time(e1) for e0, e1 in evs) / 1e3
     flops = 2.0 * (B * N + B) * d * d
     # the default forms run the bf16x3 forward (float4 rows: d % 4 == 0, aligned tables). Executed MFMA products
@@ -996,7 +1036,7 @@ def transparse_bench(w, a, device):
     dp, dk = (d + 255) // 256 * 256, (d + 15) // 16 * 16
     mfma_flops = 6 * 2.0 * B * N * dp * dk + 6 * 2.0 * B * ((d + 127) // 128 * 128) * dk
     train = None
-    if a.train_steps > 0:
+    if a.full and a.train_steps > 0:
         wts = torch.ones(B, 1, device=device)
         data = [(pos, neg, wts, torch.tensor([0])) for pos, neg in batches]
 
@@ -1079,8 +1119,8 @@ def pipeline_bench(w, a, device):
     """run.py's input pipeline in front of the train step (run.py:40-66,86-90 -> supervisor.Trainer):
     C2-shaped batches written as the reference's TFRecord files (compress_data/main.py:104-131 layout,
     17 files), read back by the C++ reader (CRC verified) on a prefetch thread, moved to the GPU and
-    trained on with kge_train_step. Reports the reader alone, the train step on device-resident
-    batches, and the end-to-end rate (the slower of the two bounds it)."""
+    trained on with kge_train_step. Reports the end-to-end rate and, with --full, the reader alone and
+    the train step on device-resident batches (the slower of the two bounds the rate)."""
     import shutil
     import tempfile
 
@@ -1098,10 +1138,14 @@ def pipeline_bench(w, a, device):
     try:
         paths = tfrecord.write_file_tfrecords(host * 4, d, B, split_number=17)
         nbytes = sum(os.path.getsize(p) for p in paths)
-        # the reader alone (one pass over every file, no prefetch thread)
-        t0 = time.perf_counter()
-        nrec = sum(1 for _ in tfrecord.load_batches(paths, B, repeat=False, prefetch=0))
-        read_s = (time.perf_counter() - t0) / nrec
+        side = {}
+        if a.full:
+            # the reader alone (one pass over every file, no prefetch thread)
+            t0 = time.perf_counter()
+            nrec = sum(1 for _ in tfrecord.load_batches(paths, B, repeat=False, prefetch=0))
+            read_s = (time.perf_counter() - t0) / nrec
+            side = {"reader_ms_per_batch": read_s * 1e3, "reader_mb_per_s": nbytes / (read_s * nrec) / 1e6,
+                    "tfrecord_bytes_per_batch": nbytes / nrec}
         # train step on device-resident batches vs fed from the files
         data = [(p.to(device), n.to(device), wt.to(device), md) for p, n, wt, md in host]
 
@@ -1115,13 +1159,17 @@ def pipeline_bench(w, a, device):
                 tr.train_step(it)
             torch.cuda.synchronize()
             t = time.perf_counter()
+            loss = None
             for _ in range(steps):
-                tr.train_step(it)
+                loss = tr.train_step(it)
             torch.cuda.synchronize()
-            return (time.perf_counter() - t) / steps
+            return (time.perf_counter() - t) / steps, loss
 
-        resident_s = run(cycle(), a.steps)
-        fed_s = run(iter(tfrecord.load_batches(paths, B, repeat=True, prefetch=4)), a.steps)
+        if a.full:
+            side["train_step_resident_ms"] = run(cycle(), a.steps)[0] * 1e3
+        fed_s, loss = run(iter(tfrecord.load_batches(paths, B, repeat=True, prefetch=4)), a.steps)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, ("loss",), loss)
     finally:
         shutil.rmtree(d, ignore_errors=True)
     return {"metric": "scored (pos+neg) triples/sec through the train step fed from TFRecord files, "
@@ -1130,9 +1178,7 @@ def pipeline_bench(w, a, device):
             "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic C2 batches written as reference-layout TFRecord files (17 files), read back",
             "config": {"workload": "run.py pipeline: " + w["name"], "global_batch": B, "n_neg": N,
-                       "parallelism": "single"},
-            "reader_ms_per_batch": read_s * 1e3, "reader_mb_per_s": nbytes / (read_s * nrec) / 1e6,
-            "train_step_resident_ms": resident_s * 1e3, "tfrecord_bytes_per_batch": nbytes / nrec}
+                       "parallelism": "single"}, **side}
 
 
 def cpu_baseline(w, budget_s=15.0, rows=64):
@@ -1283,7 +1329,7 @@ def sharded_watchdog(line, rank, timeout_s):
 
 def sharded_single(line, ws, sa, device):
     """c4s at one GPU: the unsharded fused forward through ShardedKGE (no exchange at one rank)."""
-    el = sharded_bench(ws, sa, 1, 0, device, False)
+    el, _ = sharded_bench(ws, sa, 1, 0, device, False)
     line["yago3_10_rowshard"] = {
         "workload": ws["name"], "n_gpus": 1, "global_batch": ws["B"], "n_neg": ws["N"],
         "triples_per_s": (ws["B"] * ws["N"] + ws["B"]) * sa.steps / el,
@@ -1301,7 +1347,7 @@ def sharded_lines(line, a, world, rank, device, dist):
         line["yago3_10_rowshard"] = rowshard_multi(ws, sa, world, rank, device)
     else:
         sharded_single(line, ws, sa, device)
-    el = sharded_bench(ws, sa, world, rank, device, dist, train=True)
+    el, _ = sharded_bench(ws, sa, world, rank, device, dist, train=True)
     if dist:
         el = _max_over_ranks(el, device)
     line["yago3_10_rowshard_train"] = {
@@ -1323,6 +1369,11 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS) + ["pipeline"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: roofline detail, train "
+                         "step, row-sharded sections, CPU baseline (the options below size or drop them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--train-steps", type=int, default=50, help="train-step side measurement (0 = skip)")
@@ -1372,7 +1423,9 @@ def main(argv=None):
             tdist.destroy_process_group()
         return
     if w.get("sharded"):
-        elapsed = sharded_bench(w, a, world, rank, device, dist, train=a.sharded_train)
+        elapsed, last = sharded_bench(w, a, world, rank, device, dist, train=a.sharded_train)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, ("loss",) if a.sharded_train else STEP_OUTPUTS[:3], last)
         if dist:
             t = torch.tensor([elapsed], device=device, dtype=torch.float64)
             tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
@@ -1409,7 +1462,8 @@ def main(argv=None):
 
     # kernel timing: event pairs bracket groups of `ev_group` consecutive launches (every other
     # group), so the event packets are amortised over several kernels and kept off most launches
-    # (a bracket around every single launch adds ~3 us to each step)
+    # (a bracket around every single launch adds ~3 us to each step). Only --full reads them (full_sections);
+    # they are recorded in every run, so that the timed loop is the same with and without it
     ev_group = max(1, a.event_group)
     evs = {}
     barrier()
@@ -1422,13 +1476,51 @@ def main(argv=None):
             evs[g] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             evs[g][0].record()
         h0 = time.perf_counter()
-        runner(a.warmup + i)  # continues the warmup's plan chain: one plan per timed step, made inside it
+        last = runner(a.warmup + i)  # continues the warmup's plan chain: one plan per timed step, made inside it
         host_us.append((time.perf_counter() - h0) * 1e6)
         if g in evs and r == ev_group - 1:
             evs[g][1].record()
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:  # before --full's runs reuse the runner's output sets
+        dump_outputs(a.dump_outputs, STEP_OUTPUTS, last)
+    if dist:
+        t = torch.tensor([elapsed], device=device, dtype=torch.float64)
+        tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    line = {
+        "metric": METRIC if a.workload == "c2" else f"scored (pos+neg) triples/sec, {w['name']}",
+        "value": (B * N + B) * a.steps * world / elapsed,
+        "unit": "triples/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": elapsed / a.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic U(-(gamma+2)/d,(gamma+2)/d) tables (seed 0); positives: " + m.positives_source +
+                "; negatives RandomState(2).randint(E); 8 distinct batches resident in HBM, mode alternating head/tail",
+        "config": {"workload": w["name"], "global_batch": B * world, "n_neg": N, "hidden_dim": w["hidden_dim"],
+                   "score_function": w["fn"], "parallelism": f"replicas{world}" if world > 1 else "single"},
+        "build": kge.build_id(),
+    }
+    if a.full:
+        full_sections(line, a, w, m, batches, fn, runner, evs, host_us, world, rank, device, dist)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if dist:
+        tdist.destroy_process_group()
+
+
+def full_sections(line, a, w, m, batches, fn, runner, evs, host_us, world, rank, device, dist):
+    """--full, after the headline's timed steps (main): the roofline object of the step (the timed loop's event
+    groups, then per-mode and planned / unplanned runs of their own), the train step, the YAGO3-10 row-sharded
+    sections and the CPU baseline, added to `line`."""
+    B, N = w["B"], w["N"]
+    ev_group = max(1, a.event_group)
     kern_ms = [evs[g][0].elapsed_time(evs[g][1]) / ev_group for g in sorted(evs)]
     # SURVEY §8d per-mode STEP times (both launches of a step and the gap between them, device time), after the
     # timed region, timed like kern_ms: a group of ev_group same-mode steps is queued first (untimed, it keeps
@@ -1471,10 +1563,6 @@ def main(argv=None):
     head_ms, tail_ms = [per_mode[0]], [per_mode[1]]
     if not kern_ms:  # fewer steps than one event group
         kern_ms = head_ms + tail_ms
-    if dist:
-        t = torch.tensor([elapsed], device=device, dtype=torch.float64)
-        tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
-        elapsed = float(t.item())
 
     neg_bytes, pos_bytes = algorithmic_bytes(w)
     step_bytes = neg_bytes + pos_bytes  # the fused kernel moves both calls' bytes
@@ -1488,25 +1576,7 @@ def main(argv=None):
     ent_dim_, _, _, _ = dims(w)
     pos0, neg0 = batches[0]
     uniq = torch.unique(torch.cat([neg0.reshape(-1), pos0[:, 0], pos0[:, 2]])).numel()
-    triples = (B * N + B) * a.steps * world
-    value = triples / elapsed
-    line = {
-        "metric": METRIC if a.workload == "c2" else f"scored (pos+neg) triples/sec, {w['name']}",
-        "value": value,
-        "unit": "triples/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": elapsed / a.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic U(-(gamma+2)/d,(gamma+2)/d) tables (seed 0); positives: " + m.positives_source +
-                "; negatives RandomState(2).randint(E); 8 distinct batches resident in HBM, mode alternating head/tail",
-        "config": {"workload": w["name"], "global_batch": B * world, "n_neg": N, "hidden_dim": w["hidden_dim"],
-                   "score_function": w["fn"], "parallelism": f"replicas{world}" if world > 1 else "single"},
-        "roofline": roofline_hbm(
+    line["roofline"] = roofline_hbm(
             step_bytes, traffic, traffic_src, kern_avg_s,
             l2_gather=l2_gather_roofline(pmc_l2_requests(a.workload, step_kernels), kern_avg_s),
             kernel={0: "step_fwd_kernel (negatives + positives + row reductions, one launch)",
@@ -1524,9 +1594,7 @@ def main(argv=None):
             plan_ab=("device us per step, medians of three interleaved blocks of planned and unplanned steps "
                      "after the timed region"),
             host_us_per_step_median=statistics.median(host_us), event_group_step_us=[x * 1e3 for x in kern_ms],
-            unique_row_bytes_per_step=uniq * ent_dim_ * 4, row_reuse=(B * N + 2 * B) / max(1, uniq)),
-        "build": kge.build_id(),
-    }
+            unique_row_bytes_per_step=uniq * ent_dim_ * 4, row_reuse=(B * N + 2 * B) / max(1, uniq))
     if a.train_steps > 0:
         line["train_step"] = train_step_bench(m, batches, a.train_steps, 5)
     if a.sharded_steps > 0 and a.workload == "c2":
@@ -1547,10 +1615,6 @@ def main(argv=None):
                 dog.cancel()
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(w, a.cpu_budget)
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if dist:
-        tdist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -65,6 +65,38 @@ def test_gpus1_dry_run_is_single_process():
     assert line["n_gpus"] == 1
 
 
+def test_dump_outputs_writes_named_float_arrays(tmp_path):
+    """--dump-outputs: one <name>.npy per returned tensor, float32 kept as computed (bitwise, NaN included),
+    anything else as float64; a single tensor takes the one name; no timed step, no file."""
+    import torch
+    f = torch.tensor([[1.5, float("nan")], [-0.0, 3.0]])
+    d = tmp_path / "a"
+    bench.dump_outputs(str(d), ("scores", "ranks"), (f, torch.arange(5)))
+    assert sorted(p.name for p in d.iterdir()) == ["ranks.npy", "scores.npy"]
+    s, r = np.load(d / "scores.npy"), np.load(d / "ranks.npy")
+    assert s.dtype == np.float32 and s.tobytes() == f.numpy().tobytes()
+    assert r.dtype == np.float64 and np.array_equal(r, np.arange(5.0))
+    bench.dump_outputs(str(tmp_path / "b"), ("loss",), torch.tensor(2.0, dtype=torch.float64))
+    assert np.load(tmp_path / "b" / "loss.npy") == 2.0
+    bench.dump_outputs(str(tmp_path / "c"), ("loss",), None)
+    assert not (tmp_path / "c").exists()
+
+
+def test_dump_outputs_samples_past_the_size_limit(tmp_path, monkeypatch):
+    """Past DUMP_LIMIT_BYTES every array keeps the same fraction of its elements, a fixed RandomState(0) sample
+    in flat order: identical from run to run, and within the limit in all."""
+    import torch
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    g = np.random.RandomState(5)
+    x, y = g.rand(50, 40).astype(np.float32), g.rand(500).astype(np.float32)  # 10 000 bytes
+    for k in ("d1", "d2"):
+        bench.dump_outputs(str(tmp_path / k), ("x", "y"), (torch.from_numpy(x), torch.from_numpy(y)))
+    sx, sy = np.load(tmp_path / "d1" / "x.npy"), np.load(tmp_path / "d1" / "y.npy")
+    assert sx.shape == (800,) and sy.shape == (200,) and sx.nbytes + sy.nbytes <= 4000
+    assert np.array_equal(sx, x.reshape(-1)[np.sort(np.random.RandomState(0).choice(2000, 800, replace=False))])
+    assert np.array_equal(sx, np.load(tmp_path / "d2" / "x.npy")) and np.array_equal(sy, np.load(tmp_path / "d2" / "y.npy"))
+
+
 def test_c2_positives_are_wn18rr_train_triples():
     w = bench.WORKLOADS["c2"]
     pos, src = bench.positives(w, 0, 3)
