@@ -91,6 +91,12 @@ SIGNATURES = {
                _c_f, _c_i, _c_p, _c_p, _c_i64, _c_p]),
     "kge_step_planner_set_modulus": (_c_i, [_c_p, _c_f]),
     "kge_step_planner_set_sweep": (_c_i, [_c_p, _c_i]),
+    "kge_step_planner_set_form": (_c_i, [_c_p, _c_i, _c_i]),
+    "kge_step_board_size": (_c_i64, []),
+    "kge_step_planner_set_board": (_c_i, [_c_p, _c_p, _c_i64]),
+    "kge_step_planner_set_lead": (_c_i, [_c_p, _c_i]),
+    "kge_step_planner_get": (_c_i, [_c_p, _c_i]),
+    "kge_step_planner_set_clocks": (_c_i, [_c_p, _c_p, _c_i64]),
     "kge_step_planner_plan": (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_i]),
     "kge_step_planner_step": (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_i, _c_p, _c_p, _c_p, _c_p]),
     "kge_step_planner_destroy": (_c_i, [_c_p]),

@@ -630,6 +630,7 @@ int tile_plan(int fn, ScoreParams& p, const kge_forms* forms = nullptr) {
     // need the waves for bytes in flight). forms->tile_waves chooses (8, 12, 16).
     const int64_t row_bytes = (int64_t)p.D * 4 * (is_split(fn) ? 2 : 1);
     p.tile_waves = row_bytes >= 4096 ? 12 : 16;
+    p.tile_depth = 2;  // (kge_step_planner_set_form chooses 1 for a planned step)
     const int fw = forms ? forms->tile_waves : 0;
     if (fw == 8 || fw == 12 || fw == 16) p.tile_waves = fw;
     const int64_t NT = (int64_t)p.tile_waves * kWave;
@@ -664,13 +665,36 @@ int tile_plan(int fn, ScoreParams& p, const kge_forms* forms = nullptr) {
 // 16-B aligned tables of these shapes, so that a plan is made without the tables. Returns the rows per group
 // (0: the tile form does not apply).
 int planned_tile_params(int fn, int64_t nentity, int64_t ent_ld, int64_t nrelation, int64_t rel_ld, int64_t rel_off,
-                        int64_t B, int64_t N, int64_t D, ScoreParams& p) {
+                        int64_t B, int64_t N, int64_t D, ScoreParams& p, const kge_forms* forms = nullptr) {
     if (B <= 0 || N <= 0 || D <= 0 || nentity <= 0 || nentity >= ((int64_t)1 << 31) || B >= ((int64_t)1 << 31))
         return 0;
     const float* tab = reinterpret_cast<const float*>((uintptr_t)4096);
     fill_indexed(p, fn, KGE_TAIL_BATCH, tab, nentity, ent_ld, tab, nrelation, rel_ld, rel_off, nullptr, nullptr, 0, B,
                  N, D, 0.f, 1.f, 0.f);
-    return tile_plan(fn, p) ? p.tile_rows : 0;
+    return tile_plan(fn, p, forms) ? p.tile_rows : 0;
+}
+
+// The form of a planned step's sweep (kge_step_planner_set_form / _set_board / _set_lead): waves per block,
+// candidate rows in flight per wave, and the lead throttle's board, tag and lead (board null: no throttle).
+struct SweepForm {
+    int waves, depth, lead, tag;
+    int* board;
+    long long* clk;
+};
+
+// The library's sweep form of a planned step per candidate row width, as tile_plan's tile_waves is: what
+// measured fastest against 12 x 2 / 16 x 2 without a board (scripts/window_probe.py).
+void planned_sweep_defaults(int fn, int64_t D, int& waves, int& depth, int& lead) {
+    const int64_t row_bytes = D * 4 * (is_split(fn) ? 2 : 1);
+    waves = row_bytes >= 4096 ? 12 : 16;
+    depth = 2;
+    lead = 0;
+    // only what was measured and passed (every round faster than every round of the form above, the median gain
+    // more than twice that form's own range); every other function and width keeps the form above. Each was
+    // measured at ONE shape (B 512, N 256, d 1000: 8 KB rows): other wide-row InterHT / RotatE shapes inherit it
+    // unmeasured
+    if (row_bytes >= 4096 && fn == KGE_INTERHT) lead = 12;  // C2 (WN18RR): 85.8 -> 82.6 us, leads 8 .. 16 within 1 us
+    if (row_bytes >= 4096 && fn == KGE_ROTATE) depth = 1;   // C3 (FB15k-237): 64.8 -> 59.4 us (12 x 2, lead 8: 61.9)
 }
 
 PlanArgs plan_args(const ScoreParams& tp, int mode, int64_t nentity, int64_t nrelation, const int64_t* pos,
@@ -858,7 +882,8 @@ static int step_forward_planned(int fn, int mode, const float* ent, int64_t nent
                                 float gamma, float emb_range, float modulus, float temperature, int adversarial,
                                 const void* plan, const int64_t* next_pos, const int64_t* next_neg,
                                 int64_t next_neg_ld, int next_mode, void* next_plan, float* neg_scores, int64_t ns_ld,
-                                float* out_neg, float* pos_scores, float* out_pos, int reverse, void* stream);
+                                float* out_neg, float* pos_scores, float* out_pos, int reverse, const SweepForm* sf,
+                                void* stream);
 
 int kge_step_forward_planned(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
                              int64_t nrelation, int64_t rel_ld, int64_t rel_off, int64_t B, int64_t N, int64_t D,
@@ -868,7 +893,8 @@ int kge_step_forward_planned(int fn, int mode, const float* ent, int64_t nentity
                              float* pos_scores, float* out_pos, void* stream) {
     return step_forward_planned(fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, B, N, D, gamma,
                                 emb_range, modulus, temperature, adversarial, plan, next_pos, next_neg, next_neg_ld,
-                                next_mode, next_plan, neg_scores, ns_ld, out_neg, pos_scores, out_pos, 0, stream);
+                                next_mode, next_plan, neg_scores, ns_ld, out_neg, pos_scores, out_pos, 0, nullptr,
+                                stream);
 }
 
 static int step_forward_planned(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
@@ -876,7 +902,8 @@ static int step_forward_planned(int fn, int mode, const float* ent, int64_t nent
                                 float gamma, float emb_range, float modulus, float temperature, int adversarial,
                                 const void* plan, const int64_t* next_pos, const int64_t* next_neg,
                                 int64_t next_neg_ld, int next_mode, void* next_plan, float* neg_scores, int64_t ns_ld,
-                                float* out_neg, float* pos_scores, float* out_pos, int reverse, void* stream) {
+                                float* out_neg, float* pos_scores, float* out_pos, int reverse, const SweepForm* sf,
+                                void* stream) {
     int rc = check_fn_mode(fn, mode);
     if (rc) return rc;
     if (mode == KGE_SINGLE) return fail(KGE_EINVAL, "kge_step_forward_planned needs a negative mode (0 or 1)");
@@ -895,7 +922,9 @@ static int step_forward_planned(int fn, int mode, const float* ent, int64_t nent
     ScoreParams p;
     fill_indexed(p, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, nullptr, nullptr, 0, B, N, D,
                  gamma, emb_range, modulus);
-    if (!R || !tile_plan(fn, p) || p.tile_rows != R)
+    // the planner's sweep form: a plan does not depend on it (the same rows per group at every wave count)
+    kge_forms fm = {-1, 0, 0, -1, sf ? sf->waves : 0, 0, 0};
+    if (!R || !tile_plan(fn, p, &fm) || p.tile_rows != R)
         return fail(KGE_ENOTSUP, "the tile form does not apply to these tables (unaligned rows, or "
                                  "kge_step_plan_size is 0): use kge_step_forward");
     p.out = neg_scores;
@@ -909,6 +938,13 @@ static int step_forward_planned(int fn, int mode, const float* ent, int64_t nent
     p.tile_pos = 1;
     p.tile_rev = reverse;
     p.tile_plan = reinterpret_cast<const int*>(plan);
+    if (sf) {
+        p.tile_depth = sf->depth;
+        p.tile_board = sf->board;
+        p.tile_tag = sf->tag;
+        p.tile_lead = sf->lead;
+        p.tile_clk = sf->clk;
+    }
     // the next batch's plan: the scoring launch's tail blocks, on the CUs its scoring blocks free up at its end
     // (C2 device time per step, alternating modes: 93.6 us; made beside the row reductions 99.5 us, as a launch
     // of its own 101.6 us, not planned 101.9 us; scripts/plan_probe.py, profiles/r05_plan_ab.txt)
@@ -939,9 +975,28 @@ struct kge_step_planner {
     // on the entity rows the step before touched last, which the Infinity Cache still holds when the table is larger
     // than it (C2's 327.5 MB: 92.8 -> 86.3 us per step, scripts/sweep_probe.py, profiles/r06_sweep_ab.txt)
     int sweep = 1;
+    // kge_step_planner_set_form / _set_lead / _set_board: 0, 0, -1 = planned_sweep_defaults' choice
+    int waves = 0, depth = 0, lead = -1;
+    int* board = nullptr;
+    long long* clk = nullptr;  // kge_step_planner_set_clocks (profiling builds)
+    int cus = 0;               // the device's CUs: the throttle needs every scoring block resident
+    int64_t groups = 0;        // row groups of a batch (8 scoring blocks each)
     int64_t steps = 0;  // steps issued
     void* stream = nullptr;
 };
+
+// what the planner's next step runs (the setters' choices over the library's), and whether its throttle runs
+static SweepForm planner_form(const kge_step_planner* sp) {
+    SweepForm f = {0, 0, 0, 0, nullptr, sp->clk};
+    planned_sweep_defaults(sp->fn, sp->D, f.waves, f.depth, f.lead);
+    if (sp->waves) f.waves = sp->waves;
+    if (sp->depth) f.depth = sp->depth;
+    if (f.waves == 8) f.depth = 2;
+    if (sp->lead >= 0) f.lead = sp->lead;
+    f.tag = (int)(sp->steps % kSweepTagMask) + 1;  // 1 .. kSweepTagMask: a zeroed board holds no entry
+    if (sp->board && f.lead > 0 && sp->groups <= kSweepBoardLine && sp->groups * 8 <= sp->cus) f.board = sp->board;
+    return f;
+}
 
 int kge_step_planner_create(kge_step_planner** out, int fn, const float* ent, int64_t nentity, int64_t ent_ld,
                             const float* rel, int64_t nrelation, int64_t rel_ld, int64_t rel_off, int64_t B, int64_t N,
@@ -974,8 +1029,77 @@ int kge_step_planner_create(kge_step_planner** out, int fn, const float* ent, in
     sp->plans[0] = plan0;
     sp->plans[1] = plan1;
     sp->stream = stream;
+    ScoreParams tp;
+    sp->groups = plan_groups(B, planned_tile_params(fn, nentity, ent_ld, nrelation, rel_ld, rel_off, B, N, D, tp));
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&sp->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        sp->cus = 0;  // unknown: no throttle
     *out = sp;
     return ok();
+}
+
+int kge_step_planner_set_form(kge_step_planner* sp, int waves, int depth) {
+    if (!sp) return fail(KGE_EINVAL, "kge_step_planner_set_form: null pointer");
+    if ((waves != 0 && waves != 8 && waves != 12 && waves != 16) || depth < 0 || depth > 2 || (waves == 8 && depth == 1))
+        return fail(KGE_EINVAL, "kge_step_planner_set_form: waves 0, 8, 12 or 16; depth 0, 1 or 2 (8 waves: not 1)");
+    if (waves) {  // the plans are made for the library's rows per group: the chosen block must take the same
+        ScoreParams tp, tw;
+        kge_forms fm = {-1, 0, 0, -1, waves, 0, 0};
+        if (planned_tile_params(sp->fn, sp->nentity, sp->ent_ld, sp->nrelation, sp->rel_ld, sp->rel_off, sp->B, sp->N, sp->D,
+                                tw, &fm) !=
+            planned_tile_params(sp->fn, sp->nentity, sp->ent_ld, sp->nrelation, sp->rel_ld, sp->rel_off, sp->B, sp->N, sp->D,
+                                tp))
+            return fail(KGE_ENOTSUP, "kge_step_planner_set_form: this wave count changes the rows per group");
+    }
+    sp->waves = waves;
+    sp->depth = depth;
+    return ok();
+}
+
+int64_t kge_step_board_size(void) { return (int64_t)kSweepBoardInts * 4; }
+
+int kge_step_planner_set_board(kge_step_planner* sp, void* board, int64_t board_bytes) {
+    if (!sp) return fail(KGE_EINVAL, "kge_step_planner_set_board: null pointer");
+    if (board && (board_bytes < kge_step_board_size() || !aligned(board, 4)))
+        return fail(KGE_EINVAL, "kge_step_planner_set_board: kge_step_board_size bytes, 4-B aligned");
+    sp->board = reinterpret_cast<int*>(board);
+    return ok();
+}
+
+int kge_step_planner_set_lead(kge_step_planner* sp, int lead) {
+    if (!sp) return fail(KGE_EINVAL, "kge_step_planner_set_lead: null pointer");
+    if (lead < -1 || lead >= kTileBuckets) return fail(KGE_EINVAL, "kge_step_planner_set_lead: -1, 0 or 1..255 buckets");
+    sp->lead = lead;
+    return ok();
+}
+
+int kge_step_planner_get(const kge_step_planner* sp, int what) {
+    if (!sp) return -1;
+    const SweepForm f = planner_form(sp);
+    switch (what) {
+        case KGE_PLANNER_WAVES: return f.waves;
+        case KGE_PLANNER_DEPTH: return f.depth;
+        case KGE_PLANNER_LEAD: return f.lead;
+        case KGE_PLANNER_THROTTLE: return f.board != nullptr;
+        case KGE_PLANNER_TAG: return f.tag;
+        default: return -1;
+    }
+}
+
+int kge_step_planner_set_clocks(kge_step_planner* sp, void* clocks, int64_t clocks_bytes) {
+#ifdef KGE_PROFILING_KNOBS
+    if (!sp) return fail(KGE_EINVAL, "kge_step_planner_set_clocks: null pointer");
+    if (clocks && (clocks_bytes < sp->groups * 8 * kSweepClkMarks * 8 || !aligned(clocks, 8)))
+        return fail(KGE_EINVAL, "kge_step_planner_set_clocks: 8 * groups * 48 bytes, 8-B aligned");
+    sp->clk = reinterpret_cast<long long*>(clocks);
+    return ok();
+#else
+    (void)sp;
+    (void)clocks;
+    (void)clocks_bytes;
+    return fail(KGE_ENOTSUP, "kge_step_planner_set_clocks: a -DKGE_PROFILING_KNOBS build only");
+#endif
 }
 
 int kge_step_planner_set_modulus(kge_step_planner* sp, float modulus) {
@@ -1007,11 +1131,12 @@ int kge_step_planner_step(kge_step_planner* sp, const int64_t* next_pos, const i
     if (!sp) return fail(KGE_EINVAL, "kge_step_planner_step: null pointer");
     if (sp->cur < 0) return fail(KGE_EINVAL, "kge_step_planner_step: no batch planned (kge_step_planner_plan first)");
     const bool nxt = next_pos && next_neg;
+    const SweepForm sf = planner_form(sp);
     const int rc = step_forward_planned(
         sp->fn, sp->mode, sp->ent, sp->nentity, sp->ent_ld, sp->rel, sp->nrelation, sp->rel_ld, sp->rel_off, sp->B,
         sp->N, sp->D, sp->gamma, sp->emb_range, sp->modulus, sp->temperature, sp->adversarial, sp->plans[sp->cur],
         next_pos, next_neg, next_neg_ld, next_mode, nxt ? sp->plans[1 - sp->cur] : nullptr, neg_scores, sp->N, out_neg,
-        pos_scores, out_pos, sp->sweep ? (int)(sp->steps & 1) : 0, sp->stream);
+        pos_scores, out_pos, sp->sweep ? (int)(sp->steps & 1) : 0, &sf, sp->stream);
     if (rc) return rc;
     ++sp->steps;
     if (nxt) {

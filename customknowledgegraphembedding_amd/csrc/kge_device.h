@@ -862,7 +862,11 @@ step_fwd_xcd_kernel(ScoreParams p) {
 //      against a zero row), plus, with tile_pos, each row's positive whose tail falls there, are counting-
 //      sorted into kTileBuckets entity buckets in LDS (order inside a bucket: arbitrary);
 //   3. the block's NWV waves (12 for candidate rows of 4 KB or more, else 16) take the sorted list round-robin,
-//      two candidate rows in flight per wave; head-batch positives (their own (h, r) query) after the sweep.
+//      DEPTH (2; 1 where a planned step chooses it) candidate rows in flight per wave; head-batch positives
+//      (their own (h, r) query) after the sweep. A planned step may pass a progress board (kge_internal.h:
+//      kSweepBoardInts): wave 0 publishes the entity bucket it has reached, and a wave naps once before an item
+//      that leads another block of its slice by more than p.tile_lead buckets, so the slice's blocks stay inside
+//      one L2 window. No wait depends on the board; the scores do not depend on DEPTH or the board.
 // The block sweeps its slice in ONE ascending front, and the ~32 blocks of an XCD sweep the same slice
 // together, so the ~3.4 gathers of an entity row (C2) are issued by one XCD close in time and the repeats
 // hit its L2. Against step_fwd_xcd_kernel (one wave per (row, slice, phase), which rebuilds its row's query
@@ -1086,8 +1090,9 @@ __global__ __launch_bounds__(NWV * kWave) void tile_plan_kernel(PlanArgs a) {
     tile_plan_group<NWV>(a, (int)blockIdx.x, reinterpret_cast<int*>(plan_smem));
 }
 
-template <int FN, bool CH, int V, int G, int NWV>
+template <int FN, bool CH, int V, int G, int NWV, int DEPTH>
 __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams p) {
+    static_assert(DEPTH == 1 || DEPTH == 2, "candidate rows in flight per wave");
     extern __shared__ __attribute__((aligned(16))) unsigned char tile_smem[];
     constexpr int NQ = tile_nq(FN);
     constexpr int W = G * kWave;
@@ -1390,12 +1395,32 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
     const int cnt = pl ? pcnt : cntp[0];
 
     if (p.tile_dry) return;
-    // 3. the sweep: wave w takes items w, w + NWV, w + 2 NWV, ...; the next item's
+    // 3. the sweep: wave w takes items w, w + NWV, w + 2 NWV, ...; with DEPTH 2 the next item's
     // candidate row (and InterHT's relation third) is in flight while this one is scored
     struct Item {
         Cand<FN, V, G> c;
         vecf<V> q2[FN == KGE_INTERHT ? G : 1];
     };
+    // the progress board of a planned step (kge_internal.h: kSweepBoardInts) as a buffer over this slice's line
+    // (range-checked by the hardware: a store past the line is dropped). Lane l < 32 reads row group l's entry;
+    // bv is the line as loaded with the item before (no dependent round trip); thread 0 publishes
+    const bool has_board = pl && p.tile_board && (p.tile_blocks >> 3) <= kSweepBoardLine;
+    const rsrc_t brs = make_rsrc(has_board ? p.tile_board + x * kSweepBoardLine : nullptr, has_board ? kSweepBoardLine * 4u : 0u);
+    const uint32_t boff_ld = (uint32_t)(lane & (kSweepBoardLine - 1)) * 4u;
+    const uint32_t boff_st = t == 0 ? (uint32_t)gi * 4u : kSweepBoardLine * 4u;  // past the line: dropped
+    const int btag = p.tile_tag << kSweepTagShift;
+    const bool bpeer = has_board && lane < (p.tile_blocks >> 3) && lane != gi;  // another existing row group
+    int bv = 0;
+#ifdef KGE_PROFILING_KNOBS
+    // clock marks of the block (wave 0): sweep start, past entity buckets 64 / 128 / 192 (mirrored under a
+    // descending sweep), sweep end; then the XCC id
+    long long* const clk = (pl && p.tile_clk && w == 0) ? p.tile_clk + ((int64_t)x * (p.tile_blocks >> 3) + gi) * kSweepClkMarks : nullptr;
+    int cmark = 0;
+    if (clk && lane == 0) {
+        clk[0] = wall_clock64();
+        clk[5] = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15;  // HW_REG_XCC_ID, bits 3:0
+    }
+#endif
     for (int c0 = w; c0 < cnt; c0 += NT) {
         const int nc = min(kWave, (cnt - c0 + NWV - 1) / NWV);
         int code = 0;
@@ -1447,19 +1472,52 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
                 return cand_score<FN, CH, V, G>(it.c, q, p);
             }
         };
+        // the item's progress along the slice: its entity bucket (any monotone map of the row serves; out-of-range
+        // ids sort first), mirrored under a descending sweep
+        const int my_bk = my_id >= e_lo ? max(0, min(kTileBuckets - 1, (int)((float)(int)(my_id - e_lo) * bscale))) : 0;
+        const int my_prog = p.tile_rev ? kTileBuckets - 1 - my_bk : my_bk;
+        // an item's loads, behind the lead throttle: at most one fixed nap per item, whatever the board holds
+        auto fetch = [&](Item& it, int j) {
+            const int own = __builtin_amdgcn_readlane(my_prog, j);
+            if (has_board) {  // block-uniform: without a board the sweep issues none of this (at C4's 2 KB rows
+                // the board's instructions alone, on a 0-byte buffer, cost 7.7 %: profiles/r07_bench_ab_first.txt)
+                const bool led = bpeer && (bv & ~kSweepDone) == btag && (bv & kSweepDone) + p.tile_lead < own;
+                if (__ballot(led)) __builtin_amdgcn_s_sleep(kSweepNap);
+                vecf<1> pub;
+                pub.a[0] = __int_as_float(btag | own);
+                bstore<1>(brs, boff_st, pub);
+                bv = (int)__builtin_amdgcn_raw_buffer_load_b32(brs, boff_ld, 0, kAuxSC1);
+            }
+#ifdef KGE_PROFILING_KNOBS
+            if (clk) {
+                while (cmark < 3 && own >= 64 * (cmark + 1)) {
+                    ++cmark;
+                    if (lane == 0) clk[cmark] = wall_clock64();
+                }
+            }
+#endif
+            load(it, j);
+        };
         float my_score = 0.f;
-        {
+        if constexpr (DEPTH == 2) {
             Item x0, x1;
-            load(x0, 0);
+            fetch(x0, 0);
             for (int j = 0; j < nc; j += 2) {
-                if (j + 1 < nc) load(x1, j + 1);
+                if (j + 1 < nc) fetch(x1, j + 1);
                 float s = score(x0, j);
                 if (lane == j) my_score = s;
                 if (j + 1 < nc) {
-                    if (j + 2 < nc) load(x0, j + 2);
+                    if (j + 2 < nc) fetch(x0, j + 2);
                     s = score(x1, j + 1);
                     if (lane == j + 1) my_score = s;
                 }
+            }
+        } else {
+            Item x0;
+            for (int j = 0; j < nc; ++j) {
+                fetch(x0, j);
+                const float s = score(x0, j);
+                if (lane == j) my_score = s;
             }
         }
         if (lane < nc) {
@@ -1473,6 +1531,14 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
             }
         }
     }
+    if (has_board) {  // nobody naps for a block whose sweep has ended
+        vecf<1> pub;
+        pub.a[0] = __int_as_float(btag | kSweepDone);
+        bstore<1>(brs, boff_st, pub);
+    }
+#ifdef KGE_PROFILING_KNOBS
+    if (clk && lane == 0) clk[4] = wall_clock64();
+#endif
     if constexpr (CH) {
         if (!p.tile_pos) return;
         // head-batch positives whose tail falls in this slice: the single-mode (h, r) query, tail formula
@@ -3477,13 +3543,15 @@ namespace kge_impl {
 // ---------------------------------------------------------------------------------------------
 // dispatch over (kind, candidate side, vector width, groups per lane) for one score function
 // ---------------------------------------------------------------------------------------------
-template <int FN, bool CH, int V, int G, int NWV>
+template <int FN, bool CH, int V, int G, int NWV, int DEPTH = 2>
 void launch_tile(const ScoreParams& p, hipStream_t st, int blocks) {
     // up to the whole 160 KB of a CU's LDS per block (set once per instantiation)
-    static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(step_fwd_tile_kernel<FN, CH, V, G, NWV>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, kTileLdsMax) == hipSuccess;
+    static const bool lds_ok =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, kTileLdsMax) == hipSuccess;
     (void)lds_ok;
-    hipLaunchKernelGGL((step_fwd_tile_kernel<FN, CH, V, G, NWV>), dim3(blocks), dim3(NWV * kWave), p.tile_lds, st, p);
+    hipLaunchKernelGGL((step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH>), dim3(blocks), dim3(NWV * kWave), p.tile_lds, st,
+                       p);
 }
 
 template <int FN, bool CH, int V, int G>
@@ -3514,10 +3582,12 @@ void launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
         hipLaunchKernelGGL((step_fwd_xcd_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
     else if (kind == KIND_STEP_FWD_TILE || kind == KIND_SCORE_TILE) {
         if constexpr (G <= kFwdGradMaxG) {
+            // (waves, candidate rows in flight per wave): 8 x 2, 12 x 2, 12 x 1, 16 x 2, 16 x 1
+            const bool d1 = p.tile_depth == 1;
             if (p.tile_waves == 16)
-                launch_tile<FN, CH, V, G, 16>(p, st, blocks);
+                d1 ? launch_tile<FN, CH, V, G, 16, 1>(p, st, blocks) : launch_tile<FN, CH, V, G, 16>(p, st, blocks);
             else if (p.tile_waves == 12)
-                launch_tile<FN, CH, V, G, 12>(p, st, blocks);
+                d1 ? launch_tile<FN, CH, V, G, 12, 1>(p, st, blocks) : launch_tile<FN, CH, V, G, 12>(p, st, blocks);
             else
                 launch_tile<FN, CH, V, G, 8>(p, st, blocks);
         }

@@ -52,6 +52,24 @@ constexpr int shard_nq(int fn) {
 constexpr int kFwdGradMaxG = 4;  // the fused forward + query gradient keeps 6 accumulators per element
 
 // ---------------------------------------------------------------------------------------------
+// The planned tile sweep's progress board (kge_step_planner_set_board): one 128-B line per entity slice, one
+// int per row group. Wave 0 of the scoring block (group g, slice x) publishes at board[x * 32 + g] the entity
+// bucket of the item it is taking (mirrored under a descending sweep, so progress always ascends; kSweepDone
+// when its sweep has ended) as (tag << kSweepTagShift) | progress, tag = the planner's step sequence number.
+// Every wave of the slice's blocks reads the line and naps once before an item that leads another block's
+// entry of the same tag by more than `lead` buckets. A performance hint only: no wait depends on the board,
+// so any content (garbage, entries of earlier steps, a wrapped tag) costs at most one nap per item per wave.
+// The board is used only while every scoring block is resident (blocks <= the device's CUs, so groups <= 32).
+// ---------------------------------------------------------------------------------------------
+constexpr int kSweepBoardLine = 32;                   // ints per slice line (128 B)
+constexpr int kSweepBoardInts = 8 * kSweepBoardLine;  // the whole board
+constexpr int kSweepTagShift = 9;                     // progress: 0 .. kTileBuckets - 1, kSweepDone
+constexpr int kSweepDone = (1 << kSweepTagShift) - 1;
+constexpr int kSweepTagMask = (1 << (31 - kSweepTagShift)) - 1;
+constexpr int kSweepNap = 8;  // s_sleep units of 64 clocks: ~0.2 us, about a tenth of a wave's time per item at C2
+constexpr int kSweepClkMarks = 6;  // per block: sweep start, wave 0 past buckets 64 / 128 / 192, sweep end, XCC id
+
+// ---------------------------------------------------------------------------------------------
 // The tile scorer's step plan (kge_step_plan / kge_step_forward_planned): everything step_fwd_tile_kernel
 // derives from a batch's ids alone, made ahead of the step. int32 words:
 //   [0, kPlanHdr)                 header: magic, B, N, mode, rows per group R, nentity, the relation sort flag
@@ -119,7 +137,12 @@ struct ScoreParams {
     int tile_pos;         // step_fwd_tile_kernel: also score the rows' positives (kge_step_forward)
     int tile_q2slots;     // step_fwd_tile_kernel (InterHT): LDS slots of relation thirds
     int tile_sort;        // step_fwd_tile_kernel: 0, or the power of two >= B of the (relation, row) sort
-    int tile_waves;       // step_fwd_tile_kernel: waves per block (8 or 16)
+    int tile_waves;       // step_fwd_tile_kernel: waves per block (8, 12 or 16)
+    int tile_depth;       // step_fwd_tile_kernel: candidate rows in flight per wave (1 or 2; 0 = 2)
+    int* tile_board;      // step_fwd_tile_kernel: the sweep's progress board (kSweepBoardInts ints), or null
+    int tile_tag;         // ... this step's tag of its entries (entries of another tag are ignored)
+    int tile_lead;        // ... buckets a wave may lead the slice's slowest published block before it naps
+    long long* tile_clk;  // step_fwd_tile_kernel: per-block clock marks (a -DKGE_PROFILING_KNOBS build), or null
     int tile_dry;         // step_fwd_tile_kernel: setup only, no scoring (A/B knob KGE_TILE_DRY)
     int tile_rev;         // step_fwd_tile_kernel: sweep each block's sorted list in descending entity order
     const int* tile_plan; // step_fwd_tile_kernel: this batch's plan (kge_step_forward_planned), or null

@@ -202,6 +202,11 @@ class StepPlanner:
             _stream(ent.device)), "kge_step_planner_create")
         self._h = h.value
         self._lib = lib
+        # the sweep's progress board (kge_step_planner_set_board): the library decides per step whether its lead
+        # throttle runs (its default lead for the row width; every scoring block resident)
+        self.board = torch.empty(int(lib.kge_step_board_size()), dtype=torch.uint8, device=ent.device)
+        check(lib.kge_step_planner_set_board(self._h, self.board.data_ptr(), self.board.numel()),
+              "kge_step_planner_set_board")
         self._step_fn = lib.kge_step_planner_step
         self._planned = False
         self._held = None      # the tensors the waiting plan was made from (kept alive until its step)
@@ -229,8 +234,24 @@ class StepPlanner:
             raise ValueError("pos must be contiguous and neg row-contiguous")
 
     def set_sweep(self, alternate):
-        """1: the tile sweep's direction alternates step by step (kge_step_planner_set_sweep); 0: ascending."""
+        """1 (the default): the tile sweep's direction alternates step by step (kge_step_planner_set_sweep);
+        0: always ascending."""
         check(self._lib.kge_step_planner_set_sweep(self._h, int(alternate)), "kge_step_planner_set_sweep")
+
+    def set_form(self, waves=0, depth=0):
+        """The sweep's waves per block (8, 12, 16) and candidate rows in flight per wave (1, 2); 0: the library's
+        choice for the row width (kge_step_planner_set_form)."""
+        check(self._lib.kge_step_planner_set_form(self._h, int(waves), int(depth)), "kge_step_planner_set_form")
+
+    def set_lead(self, lead):
+        """The lead throttle: buckets (1..255) a wave may lead the slowest block of its slice before it naps once;
+        0: off; -1: the library's choice for the row width (kge_step_planner_set_lead)."""
+        check(self._lib.kge_step_planner_set_lead(self._h, int(lead)), "kge_step_planner_set_lead")
+
+    def form(self):
+        """What the next step runs: {"waves", "depth", "lead", "throttle", "tag"} (kge_step_planner_get)."""
+        return {k: int(self._lib.kge_step_planner_get(self._h, i))
+                for i, k in enumerate(("waves", "depth", "lead", "throttle", "tag"))}
 
     def set_modulus(self, modulus):
         check(self._lib.kge_step_planner_set_modulus(self._h, float(modulus)), "kge_step_planner_set_modulus")
