@@ -1579,6 +1579,13 @@ static StepWs step_ws_layout(char* base, int64_t E, int64_t B, int64_t N, int64_
 
 static int64_t ent_width(int fn, int64_t D) { return is_split(fn) ? 2 * D : D; }
 static int64_t rel_width(int fn, int64_t D) { return fn == KGE_COMPLEX ? 2 * D : D; }
+// Columns of a relation row that belong to the table (the rest of rel_ld is the caller's padding, which no
+// entry point writes): InterHT rows hold three thirds (model.py:209) of which one is read; every other
+// function reads its whole row. Never less than the part read, never more than the row stride.
+static int64_t rel_table_width(int fn, int64_t D, int64_t rel_off, int64_t rel_ld) {
+    const int64_t w = std::max(fn == KGE_INTERHT ? 3 * D : rel_width(fn, D), rel_off + rel_width(fn, D));
+    return std::min(w, rel_ld);
+}
 
 int64_t kge_score_bwd_workspace_size(int fn, int mode, int64_t B, int64_t N, int64_t D) {
     (void)fn;
@@ -1672,13 +1679,19 @@ static int step_backward_impl(int fn, int mode, const float* ent, int64_t nentit
     if (B * N + 3 * B >= (int64_t)INT32_MAX || nentity >= (int64_t)INT32_MAX)
         return fail(KGE_EINVAL, "too many gradient events for 32-bit codes");
     const int64_t ent_w = ent_width(fn, D), rel_w = rel_width(fn, D);
-    const int64_t rel_dim = rel_ld;  // rows are written over their full stride (padding included)
+    // relation rows are written over the table's width (the parts no score function reads get a zero
+    // gradient), never over the padding of a row stride wider than the table
+    const int64_t rel_dim = rel_table_width(fn, D, rel_off, rel_ld);
     StepWs w = step_ws_layout((char*)workspace, nentity, B, N, D, ent_w, rel_w);
     if (!workspace || workspace_bytes < w.bytes) return fail(KGE_EINVAL, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     if (B == 0 && !adam) {
-        if (hipMemsetAsync(d_ent, 0, (size_t)(nentity * ent_ld * 4), st) != hipSuccess ||
-            hipMemsetAsync(d_rel, 0, (size_t)(nrelation * rel_ld * 4), st) != hipSuccess)
+        // the tables' columns only: the last row of a padded buffer may end at its width
+        if ((nentity > 0 && hipMemset2DAsync(d_ent, (size_t)(ent_ld * 4), 0, (size_t)(ent_w * 4), (size_t)nentity,
+                                             st) != hipSuccess) ||
+            (nrelation > 0 && rel_dim > 0 &&
+             hipMemset2DAsync(d_rel, (size_t)(rel_ld * 4), 0, (size_t)(rel_dim * 4), (size_t)nrelation, st) !=
+                 hipSuccess))
             return check_launch("kge_step_backward memset");
         if (d_modulus && hipMemsetAsync(d_modulus, 0, 4, st) != hipSuccess) return check_launch("memset");
         return ok();

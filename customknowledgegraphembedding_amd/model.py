@@ -53,6 +53,24 @@ def _dims_for(model_name, entity_dim, relation_dim):
     raise ValueError(f"model {model_name} not supported")
 
 
+def check_adam_moments(param, state):
+    """The fused train steps address m / v with the PARAMETER's leading dimension (kge_hip.h: m_ent and
+    v_ent use ent_ld, m_rel and v_rel use rel_ld), so a moment laid out differently from its parameter
+    (a dense moment of a row-padded table, a state restored with other strides) would be read and
+    written out of place, past its end for a padded table. Refuse it before any pointer is passed."""
+    for key in ("exp_avg", "exp_avg_sq"):
+        mom = state[key]
+        same = tuple(mom.shape) == tuple(param.shape) and all(
+            n <= 1 or a == b for n, a, b in zip(param.shape, mom.stride(), param.stride()))
+        if not same:
+            raise ValueError(
+                f"Adam moment {key} has shape {tuple(mom.shape)} / strides {tuple(mom.stride())} but its "
+                f"parameter has {tuple(param.shape)} / {tuple(param.stride())}: the fused step addresses "
+                "both with the parameter's leading dimension")
+        if mom.dtype != torch.float32 or mom.device != param.device:
+            raise ValueError(f"Adam moment {key} must be float32 on {param.device}")
+
+
 class _KGEBase(nn.Module):
     """Tables + the fused scoring entry shared by both model classes."""
 
@@ -227,7 +245,8 @@ class TFKGEModel(_KGEBase):
           one_call=False (and pRotatE): kge_step_forward, kge_step_loss, kge_step_backward_adam —
             bitwise equal to the autograd path (kge_step_backward + kge_adam_update).
           loss_sum: optional 0-dim fp32 device tensor the loss is added to (one_call only; a running
-            Sum metric updated inside the step's last kernel)."""
+            Sum metric updated inside the step's last kernel).
+        Raises ValueError when an Adam moment is not laid out like its parameter (check_adam_moments)."""
         from .optim import Adam
         from . import _lib
 
@@ -239,6 +258,11 @@ class TFKGEModel(_KGEBase):
         fn = FN_IDS[self.model_name]
         ent, rel = self.entity_embedding, self.relation_embedding
         is_p = self.model_name == "pRotatE"
+        # moments the optimizer already holds (restored, or made elsewhere) are checked before anything is
+        # launched; the ones this step creates are laid out like their parameter (_adam_state)
+        for prm in [ent, rel] + ([self.modulus] if is_p else []):
+            if optimizer.state[prm]:
+                check_adam_moments(prm, optimizer.state[prm])
         if one_call and not is_p:
             return self._train_step_one_call(fn, m, positive_sample, negative_sample, subsampling_weight, optimizer,
                                              loss_sum)
@@ -291,8 +315,9 @@ class TFKGEModel(_KGEBase):
             st = optimizer.state[prm]
             if not st:
                 st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(prm)
-                st["exp_avg_sq"] = torch.zeros_like(prm)
+                st["exp_avg"] = ops.like_strided(prm, zero=True)
+                st["exp_avg_sq"] = ops.like_strided(prm, zero=True)
+            check_adam_moments(prm, st)
         return group, lr, optimizer.state[self.entity_embedding]["step"] + 1
 
     @staticmethod

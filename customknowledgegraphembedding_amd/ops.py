@@ -49,6 +49,16 @@ def _i64(t, name):
         raise TypeError(f"{name} must be int64, got {t.dtype}")
 
 
+def like_strided(t, zero=False):
+    """A fresh tensor with t's shape AND strides (torch's *_like give a non-dense view dense strides).
+    Every gradient buffer that goes to the library next to its table's leading dimension comes from
+    here: the library addresses d_ent / d_rel with ent_ld / rel_ld (include/kge_hip.h) and writes only
+    the columns [0, width) of a row, so the padding of a padded view's gradient is never touched.
+    zero: for the entry points that accumulate."""
+    out = torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device)
+    return out.zero_() if zero else out
+
+
 def fn_id(name: str) -> int:
     try:
         return FN_IDS[name]
@@ -544,8 +554,8 @@ class _ScoreIndexed(torch.autograd.Function):
         ent, rel, pos, neg = ctx.saved_tensors
         fn, mode, rel_off, D, gamma, emb_range, modulus, has_neg, mod_shape = ctx.cfg
         has_mod = mod_shape is not None
-        d_ent = torch.zeros_like(ent)
-        d_rel = torch.zeros_like(rel)
+        d_ent = like_strided(ent, zero=True)
+        d_rel = like_strided(rel, zero=True)
         d_mod = torch.zeros(1, dtype=torch.float32, device=ent.device) if has_mod else None
         score_indexed_bwd_raw(fn, mode, ent, rel, rel_off, pos, neg if has_neg else None, D, gamma,
                               emb_range, modulus, d_scores, d_ent, d_rel, d_mod)
@@ -570,9 +580,9 @@ class _ScoreDense(torch.autograd.Function):
         h, hld = _rows(head)
         t, tld = _rows(tail)
         r, rld = _rows(relation)
-        dh = torch.zeros_like(h)
-        dt = torch.zeros_like(t)
-        dr = torch.zeros_like(r)
+        dh = like_strided(h, zero=True)
+        dt = like_strided(t, zero=True)
+        dr = like_strided(r, zero=True)
         d_scores = d_scores.contiguous()
         rc = _lib.load().kge_score_dense_bwd(
             fn, mode, h.data_ptr(), hld, r.data_ptr(), rld, rel_off, t.data_ptr(), tld, B, N, D,
@@ -656,8 +666,8 @@ class _StepForward(torch.autograd.Function):
         dev = ent.device
         d_neg = torch.zeros(B, device=dev) if d_neg is None else d_neg.contiguous()
         d_pos = torch.zeros(B, device=dev) if d_pos is None else d_pos.contiguous()
-        d_ent = torch.empty_like(ent)
-        d_rel = torch.empty_like(rel)
+        d_ent = like_strided(ent)
+        d_rel = like_strided(rel)
         d_mod = torch.empty(1, dtype=torch.float32, device=dev) if mod_shape is not None else None
         nbytes = lib.kge_step_backward_workspace_size(fn, ent.shape[0], B, N, D)
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
@@ -692,7 +702,7 @@ class _TranSparse(torch.autograd.Function):
     def backward(ctx, d_scores):
         ent, rel, W, mask, pos, neg, stats, M = ctx.saved_tensors
         m, has_neg, has_m = ctx.cfg
-        d_ent, d_rel, d_W = torch.zeros_like(ent), torch.zeros_like(rel), torch.zeros_like(W)
+        d_ent, d_rel, d_W = like_strided(ent, zero=True), like_strided(rel, zero=True), torch.zeros_like(W)
         transparse_score_bwd_raw(m, ent, rel, W, mask, pos, neg if has_neg else None, stats, d_scores, d_ent, d_rel,
                                  d_W, M=M if has_m else None)
         return d_ent, d_rel, d_W, None, None, None, None, None

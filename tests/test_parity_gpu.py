@@ -108,10 +108,11 @@ def _rand_case(name, D, E=300, R=9, B=5, N=37, seed=0, gamma=11.0):
 
 
 @pytest.mark.parametrize("name", FNS)
-@pytest.mark.parametrize("D", [1, 3, 50, 63, 65, 130, 257, 500, 1000, 2048])
+@pytest.mark.parametrize("D", [1, 3, 50, 63, 65, 130, 257, 500, 1000, 2048, 255, 450, 1022, 64])
 def test_odd_and_max_dims(name, D):
-    """Every vector width (16/8/4-B rows), partial groups past D, and the largest D per width."""
-    if D > 512 and D % 4:
+    """Every vector width (16/8/4-B rows), partial groups past D, and the largest D per width. With 255 (V1 G4),
+    450 (V2 G4), 1022 (V2 G8) and 64 (V4 G1) all twelve (V, G) pairs of score_fwd_kernel run."""
+    if D > 512 and D % 2:
         pytest.skip("scalar rows are register-resident only up to 512")
     ent, rel, pos, neg, gamma, rng = _rand_case(name, D, seed=D)
     mod = 0.5 * rng
