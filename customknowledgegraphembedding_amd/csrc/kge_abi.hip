@@ -384,6 +384,42 @@ int check_launch(const char* what) {
 
 bool aligned(const void* ptr, int bytes) { return ptr == nullptr || ((uintptr_t)ptr % (uintptr_t)bytes) == 0; }
 
+bool valid_fn(int fn) { return fn >= KGE_TRANSE && fn <= KGE_PROTATE; }
+
+// ---------------------------------------------------------------------------------------------
+// The problem of a call. Each entry point builds these once from its arguments, in the C-ABI's argument
+// order; everything below it takes them by const reference. Host only: never a kernel argument.
+// ---------------------------------------------------------------------------------------------
+struct Tables {  // the score function, its embedding tables and constants
+    int fn;
+    const float* ent;
+    int64_t nentity, ent_ld;
+    const float* rel;
+    int64_t nrelation, rel_ld, rel_off;
+    int64_t D;
+    float gamma, emb_range, modulus;
+};
+struct Batch {  // the triples scored
+    int mode;
+    const int64_t* pos;
+    const int64_t* neg;
+    int64_t neg_ld, B, N;
+};
+// the loss side of kge_step_backward: the forward's scores, the loss' gradients, where the table gradients go
+struct StepGrads {
+    float temperature;
+    int adversarial, detach;
+    const float* neg_scores;
+    int64_t ns_ld;
+    const float* pos_scores;
+    const float* d_out_neg;
+    const float* d_out_pos;
+    float* d_ent;
+    float* d_rel;
+    float* d_modulus;
+    const float* cand_stats;
+};
+
 // widest vector width every operand allows, then the groups-per-lane bucket
 int pick_vg(const ScoreParams& p, int& V, int& G) {
     const int cand[3] = {4, 2, 1};
@@ -434,7 +470,7 @@ int dispatch(int fn, const ScoreParams& p, int kind, hipStream_t st, int blocks,
 int check_fn_mode(int fn, int mode) {
     if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH && mode != KGE_SINGLE)
         return fail(KGE_EINVAL, "mode must be 0 (head-batch), 1 (tail-batch) or 3 (single)");
-    if (fn < KGE_TRANSE || fn > KGE_PROTATE) return fail(KGE_EINVAL, "unknown score function id " + std::to_string(fn));
+    if (!valid_fn(fn)) return fail(KGE_EINVAL, "unknown score function id " + std::to_string(fn));
     return 0;
 }
 
@@ -457,64 +493,61 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
             G = g1;
         }
     }
-    int64_t waves;
-    if (kind == KIND_FINISH) {
-        p.cpw = 1;
-        p.wpr = 1;
-        waves = p.B;
-    } else if (kind == KIND_BWD_ROWS || kind == KIND_BWD_STREAM || kind == KIND_STEP_FWD ||
-               kind == KIND_STEP_FWD_STATS || kind == KIND_STEP_FWD_GRAD || kind == KIND_SHARD_FWD_GRAD) {
-        waves = p.B * kWavesPerBlock;  // one block per slot / batch row
-    } else if (kind == KIND_STEP_FWD_TILE || kind == KIND_SCORE_TILE) {
-        if (p.tile_rows < 1 || p.tile_lds > kTileLdsMax) return fail(KGE_EINVAL, "tile plan missing");
-        // one block of tile_waves waves per (group of tile_rows batch rows, entity slice): run_score's
-        // block count is waves / kWavesPerBlock; then, for a planned step, one tail block per group of the
-        // next batch's plan
-        const int64_t groups = (p.B + p.tile_rows - 1) / p.tile_rows;
-        p.tile_blocks = (int)(groups * 8);
-        waves = (groups * 8 + (p.tile_next.plan ? plan_groups(p.tile_next.B, p.tile_next.R) : 0)) * kWavesPerBlock;
-    } else if (kind == KIND_STEP_FWD_XCD || kind == KIND_SCORE_SHARD_XCD || kind == KIND_SHARD_BUCKET) {
-        waves = (p.B + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock * 8;  // 8 slice blocks per 4 rows
-        if (kind == KIND_STEP_FWD_XCD && p.xcd_phases > 1) waves *= p.xcd_phases;
-    } else if (kind == KIND_BWD_CHAIN || kind == KIND_SHARD_POS) {
-        waves = p.B;  // one wave per slot
-    } else if (kind == KIND_STEP_EPILOGUE) {
-        // one wave per slot (negative rows' chains, positives, negative rows' score gradients), then the
-        // event-scatter blocks (about four codes per thread, at most 256 blocks), then one block for the loss
-        const int64_t ev = p.B * p.N + 3 * p.B;
-        const int64_t sb = std::min<int64_t>(std::max<int64_t>((ev + 4 * kBlock - 1) / (4 * kBlock), 1), 256);
-        waves = (3 * p.B + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock + (sb + 1) * kWavesPerBlock;
-    } else if (kind == KIND_SHARD_EPILOGUE) {
-        // one wave per slot (negative rows, then positives), then one block for the loss
-        waves = (2 * p.B + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock + kWavesPerBlock;
-    } else if (kind == KIND_BWD_ENT) {
-        waves = p.c_rows;  // one wave per entity row
-    } else if (kind == KIND_BWD_ENT_STREAM) {
-        waves = p.c_rows * kWavesPerBlock;  // one block per entity row
-    } else {
-        // sharded scoring compacts each wave's owned candidates: long runs (up to 512 ids, ~64 owned
-        // at 8 shards) keep the per-wave query build amortised; >= 8192 waves still fill the chip
-        p.cpw = p.skip_foreign ? pick_cpw_sharded(p.B, p.N) : pick_cpw(p.B, p.N);
-        p.wpr = (int)((p.N + p.cpw - 1) / p.cpw);
-        waves = p.B * p.wpr;
+    const KindInfo& k = kKinds[kind];
+    int64_t waves = 0;
+    switch (k.grid) {
+        case GRID_WAVE_PER_ROW:
+            if (kind == KIND_FINISH) p.cpw = p.wpr = 1;
+            waves = p.B;  // one wave per slot / batch row
+            break;
+        case GRID_BLOCK_PER_ROW: waves = p.B * kWavesPerBlock; break;
+        case GRID_WAVE_PER_ENT: waves = p.c_rows; break;
+        case GRID_BLOCK_PER_ENT: waves = p.c_rows * kWavesPerBlock; break;
+        case GRID_XCD_SLICES:
+            waves = (p.B + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock * 8;
+            if (kind == KIND_STEP_FWD_XCD && p.xcd_phases > 1) waves *= p.xcd_phases;
+            break;
+        case GRID_TILE_GROUPS: {
+            if (p.tile_rows < 1 || p.tile_lds > kTileLdsMax) return fail(KGE_EINVAL, "tile plan missing");
+            // one block of tile_waves waves per (group of tile_rows batch rows, entity slice): run_score's
+            // block count is waves / kWavesPerBlock; then, for a planned step, one tail block per group of the
+            // next batch's plan
+            const int64_t groups = (p.B + p.tile_rows - 1) / p.tile_rows;
+            p.tile_blocks = (int)(groups * 8);
+            waves = (groups * 8 + (p.tile_next.plan ? plan_groups(p.tile_next.B, p.tile_next.R) : 0)) * kWavesPerBlock;
+            break;
+        }
+        case GRID_CAND_PER_WAVE:
+            // sharded scoring compacts each wave's owned candidates: long runs (up to 512 ids, ~64 owned
+            // at 8 shards) keep the per-wave query build amortised; >= 8192 waves still fill the chip
+            p.cpw = p.skip_foreign ? pick_cpw_sharded(p.B, p.N) : pick_cpw(p.B, p.N);
+            p.wpr = (int)((p.N + p.cpw - 1) / p.cpw);
+            waves = p.B * p.wpr;
+            break;
+        case GRID_STEP_EPILOGUE: {
+            // one wave per slot (negative rows' chains, positives, negative rows' score gradients), then the
+            // event-scatter blocks (about four codes per thread, at most 256 blocks), then one block for the loss
+            const int64_t ev = p.B * p.N + 3 * p.B;
+            const int64_t sb = std::min<int64_t>(std::max<int64_t>((ev + 4 * kBlock - 1) / (4 * kBlock), 1), 256);
+            waves = (3 * p.B + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock + (sb + 1) * kWavesPerBlock;
+            break;
+        }
+        case GRID_SHARD_EPILOGUE:
+            // one wave per slot (negative rows, then positives), then one block for the loss
+            waves = (2 * p.B + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock + kWavesPerBlock;
+            break;
     }
     const int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > INT32_MAX) return fail(KGE_EINVAL, "problem too large for one launch");
-    const bool ch = (kind != KIND_FINISH && kind != KIND_SHARD_POS) && mode == KGE_HEAD_BATCH;
-    if ((kind == KIND_BWD_ROWS || kind == KIND_BWD_ENT || kind == KIND_BWD_STREAM || kind == KIND_BWD_CHAIN ||
-         kind == KIND_BWD_ENT_STREAM) &&
-        G > kMaxG)
-        return fail(KGE_ENOTSUP, "dimension too large");
-    if ((kind == KIND_STEP_FWD_GRAD || kind == KIND_STEP_EPILOGUE || kind == KIND_SHARD_FWD_GRAD ||
-         kind == KIND_SHARD_POS || kind == KIND_SHARD_EPILOGUE) &&
-        (G > kFwdGradMaxG || fn == KGE_PROTATE))
+    const bool ch = k.ch && mode == KGE_HEAD_BATCH;
+    if (k.no_protate && (G > k.max_g || fn == KGE_PROTATE))
         return fail(KGE_ENOTSUP, "the fused forward + query gradient needs D <= 1024 and no pRotatE");
-    if ((kind == KIND_BWD_STREAM || kind == KIND_BWD_ENT_STREAM) && G % kWavesPerBlock)
-        return fail(KGE_ENOTSUP, "the streaming backward needs G % 4 == 0");
-    rc = dispatch(fn, p, kind, (hipStream_t)stream, (int)blocks, ch, V, G);
+    if (G > k.max_g) return fail(KGE_ENOTSUP, "dimension too large");
+    if (k.g_whole_waves && G % kWavesPerBlock) return fail(KGE_ENOTSUP, "the streaming backward needs G % 4 == 0");
+    // a (kind, function, side, V, G) without an instantiation launches nothing and says so
+    rc = kind_has(kind, fn, ch, G) ? dispatch(fn, p, kind, (hipStream_t)stream, (int)blocks, ch, V, G) : KGE_ENOTSUP;
     if (rc) return fail(rc, "no kernel for this (function, width) combination");
-    return check_launch(kind == KIND_BWD ? "kge score backward launch"
-                                         : (kind == KIND_FINISH ? "kge finish launch" : "kge score launch"));
+    return check_launch(k.what);
 }
 
 float phase_div_for(int fn, float emb_range) {
@@ -523,41 +556,39 @@ float phase_div_for(int fn, float emb_range) {
     return (float)((double)emb_range / pi);
 }
 
-void fill_indexed(ScoreParams& p, int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld,
-                  const float* rel, int64_t nrelation, int64_t rel_ld, int64_t rel_off, const int64_t* pos,
-                  const int64_t* neg, int64_t neg_ld, int64_t B, int64_t N, int64_t D, float gamma, float emb_range,
-                  float modulus) {
+void fill_indexed(ScoreParams& p, const Tables& t, const Batch& b) {
     memset(&p, 0, sizeof(p));
-    const bool ch = mode == KGE_HEAD_BATCH;
-    p.qent = ent;
-    p.q_idx = pos ? pos + (ch ? 2 : 0) : nullptr;
-    p.q_ld = ent_ld;
+    const bool ch = b.mode == KGE_HEAD_BATCH;
+    p.qent = t.ent;
+    p.q_idx = b.pos ? b.pos + (ch ? 2 : 0) : nullptr;
+    p.q_ld = t.ent_ld;
     p.q_stride = 3;
-    p.q_rows = nentity;
-    p.rel = rel;
-    p.r_idx = pos ? pos + 1 : nullptr;
-    p.r_ld = rel_ld;
+    p.q_rows = t.nentity;
+    p.rel = t.rel;
+    p.r_idx = b.pos ? b.pos + 1 : nullptr;
+    p.r_ld = t.rel_ld;
     p.r_stride = 3;
-    p.r_rows = nrelation;
-    p.r_off = rel_off;
-    p.cent = ent;
-    p.c_ld = ent_ld;
-    p.c_rows = nentity;
-    if (mode == KGE_SINGLE) {
-        p.c_idx = pos ? pos + 2 : nullptr;
+    p.r_rows = t.nrelation;
+    p.r_off = t.rel_off;
+    p.cent = t.ent;
+    p.c_ld = t.ent_ld;
+    p.c_rows = t.nentity;
+    if (b.mode == KGE_SINGLE) {
+        p.c_idx = b.pos ? b.pos + 2 : nullptr;
         p.c_stride = 3;
-        N = 1;
     } else {
-        p.c_idx = neg;
-        p.c_stride = neg_ld;
+        p.c_idx = b.neg;
+        p.c_stride = b.neg_ld;
     }
-    p.B = B;
-    p.N = N;
-    p.D = (int)D;
-    p.gamma = gamma;
-    p.phase_div = phase_div_for(fn, emb_range);
-    p.modulus = modulus;
+    p.B = b.B;
+    p.N = b.mode == KGE_SINGLE ? 1 : b.N;
+    p.D = (int)t.D;
+    p.gamma = t.gamma;
+    p.phase_div = phase_div_for(t.fn, t.emb_range);
+    p.modulus = t.modulus;
 }
+// the positive (single-mode) call over the same rows
+Batch single_of(const Batch& b) { return {KGE_SINGLE, b.pos, nullptr, 0, b.B, 1}; }
 
 void fill_dense(ScoreParams& p, int fn, int mode, const float* head, int64_t head_ld, const float* rel,
                 int64_t rel_ld, int64_t rel_off, const float* tail, int64_t tail_ld, int64_t B, int64_t N, int64_t D,
@@ -664,20 +695,20 @@ int tile_plan(int fn, ScoreParams& p, const kge_forms* forms = nullptr) {
 // The tile parameters of a planned step (kge_step_plan / kge_step_forward_planned): tile_plan's choice for
 // 16-B aligned tables of these shapes, so that a plan is made without the tables. Returns the rows per group
 // (0: the tile form does not apply).
-int planned_tile_params(int fn, int64_t nentity, int64_t ent_ld, int64_t nrelation, int64_t rel_ld, int64_t rel_off,
-                        int64_t B, int64_t N, int64_t D, ScoreParams& p, const kge_forms* forms = nullptr) {
-    if (B <= 0 || N <= 0 || D <= 0 || nentity <= 0 || nentity >= ((int64_t)1 << 31) || B >= ((int64_t)1 << 31))
+int planned_tile_params(const Tables& t, int64_t B, int64_t N, ScoreParams& p, const kge_forms* forms = nullptr) {
+    if (B <= 0 || N <= 0 || t.D <= 0 || t.nentity <= 0 || t.nentity >= ((int64_t)1 << 31) || B >= ((int64_t)1 << 31))
         return 0;
-    const float* tab = reinterpret_cast<const float*>((uintptr_t)4096);
-    fill_indexed(p, fn, KGE_TAIL_BATCH, tab, nentity, ent_ld, tab, nrelation, rel_ld, rel_off, nullptr, nullptr, 0, B,
-                 N, D, 0.f, 1.f, 0.f);
-    return tile_plan(fn, p, forms) ? p.tile_rows : 0;
+    Tables a = t;
+    a.ent = a.rel = reinterpret_cast<const float*>((uintptr_t)4096);
+    fill_indexed(p, a, {KGE_TAIL_BATCH, nullptr, nullptr, 0, B, N});
+    return tile_plan(t.fn, p, forms) ? p.tile_rows : 0;
 }
 
 // The form of a planned step's sweep (kge_step_planner_set_form / _set_board / _set_lead): waves per block,
 // candidate rows in flight per wave, and the lead throttle's board, tag and lead (board null: no throttle).
 struct SweepForm {
     int waves, depth, lead, tag;
+    int rev;  // sweep each block's sorted list in descending entity order (kge_step_planner_set_sweep)
     int* board;
     long long* clk;
 };
@@ -697,21 +728,27 @@ void planned_sweep_defaults(int fn, int64_t D, int& waves, int& depth, int& lead
     if (row_bytes >= 4096 && fn == KGE_ROTATE) depth = 1;   // C3 (FB15k-237): 64.8 -> 59.4 us (12 x 2, lead 8: 61.9)
 }
 
-PlanArgs plan_args(const ScoreParams& tp, int mode, int64_t nentity, int64_t nrelation, const int64_t* pos,
-                   const int64_t* neg, int64_t neg_ld, int64_t B, int64_t N, void* plan) {
+PlanArgs plan_args(const ScoreParams& tp, const Tables& t, const Batch& b, void* plan) {
     PlanArgs a;
-    a.pos = pos;
-    a.neg = neg;
-    a.neg_ld = neg_ld;
-    a.B = B;
-    a.N = N;
-    a.nent = nentity;
-    a.nrel = nrelation;
-    a.mode = mode;
+    a.pos = b.pos;
+    a.neg = b.neg;
+    a.neg_ld = b.neg_ld;
+    a.B = b.B;
+    a.N = b.N;
+    a.nent = t.nentity;
+    a.nrel = t.nrelation;
+    a.mode = b.mode;
     a.R = tp.tile_rows;
     a.sort = tp.tile_sort != 0;
     a.plan = reinterpret_cast<int*>(plan);
     return a;
+}
+
+// the row reductions after a sliced or tiled scoring launch (kge_step_forward, kge_step_forward_planned)
+int launch_neg_rows(const ScoreParams& p, const char* what, void* stream) {
+    const int64_t blocks = (p.B + kWavesPerBlock - 1) / kWavesPerBlock;
+    hipLaunchKernelGGL(neg_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, p);
+    return check_launch(what);
 }
 
 }  // namespace
@@ -731,7 +768,7 @@ int kge_abi_version(void) { return KGE_ABI_VERSION; }
 const char* kge_last_error(void) { return g_last_error.c_str(); }
 
 int64_t kge_max_dim(int fn) {
-    if (fn < KGE_TRANSE || fn > KGE_PROTATE) return 0;
+    if (!valid_fn(fn)) return 0;
     return (int64_t)kMaxG * kWave * 4;
 }
 
@@ -756,9 +793,9 @@ int kge_score_indexed_ex(int fn, int mode, const float* ent, int64_t nentity, in
     if (!pos) return fail(KGE_EINVAL, "pos must not be NULL");
     if (mode != KGE_SINGLE && !neg) return fail(KGE_EINVAL, "neg must not be NULL in head/tail-batch mode");
     if (!scores) return fail(KGE_EINVAL, "scores must not be NULL");
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
     ScoreParams p;
-    fill_indexed(p, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N, D, gamma,
-                 emb_range, modulus);
+    fill_indexed(p, t, {mode, pos, neg, neg_ld, B, N});
     p.out = scores;
     p.out_ld = scores_ld;
     if (mode != KGE_SINGLE && nentity < ((int64_t)1 << 31) && use_xcd_order(nentity, N, forms)) {
@@ -779,9 +816,9 @@ int kge_step_finish(int fn, const float* ent, int64_t nentity, int64_t ent_ld, c
     if (B < 0 || N <= 0 || D <= 0) return fail(KGE_EINVAL, "bad shape (B, N, D)");
     if (B == 0) return ok();
     if (!pos || !neg_scores || !out_neg || !out_pos) return fail(KGE_EINVAL, "null pointer");
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
     ScoreParams f;
-    fill_indexed(f, fn, KGE_SINGLE, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, nullptr, 0, B, 1, D,
-                 gamma, emb_range, modulus);
+    fill_indexed(f, t, {KGE_SINGLE, pos, nullptr, 0, B, 1});
     f.neg_scores = neg_scores;
     f.ns_ld = ns_ld;
     f.n_neg = N;
@@ -814,9 +851,9 @@ int kge_step_forward_ex(int fn, int mode, const float* ent, int64_t nentity, int
     if (B < 0 || N <= 0 || D <= 0) return fail(KGE_EINVAL, "bad shape (B, N, D)");
     if (B == 0) return ok();
     if (!pos || !neg || !neg_scores || !out_neg || !out_pos) return fail(KGE_EINVAL, "null pointer");
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
     ScoreParams p;
-    fill_indexed(p, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N, D, gamma,
-                 emb_range, modulus);
+    fill_indexed(p, t, {mode, pos, neg, neg_ld, B, N});
     p.out = neg_scores;
     p.out_ld = ns_ld;
     p.cand_stats = reinterpret_cast<float2*>(cand_stats);
@@ -838,36 +875,37 @@ int kge_step_forward_ex(int fn, int mode, const float* ent, int64_t nentity, int
             rc = run_score(fn, mode, p, KIND_STEP_FWD_XCD, stream);
         }
         if (rc) return rc;
-        const int64_t blocks = (B + kWavesPerBlock - 1) / kWavesPerBlock;
-        hipLaunchKernelGGL(neg_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, p);
-        return check_launch("kge_step_forward row reductions");
+        return launch_neg_rows(p, "kge_step_forward row reductions", stream);
     }
     // one launch: negatives + the per-row finish (positive, reduction)
     return run_score(fn, mode, p, (cand_stats && fn == KGE_INTERHT) ? KIND_STEP_FWD_STATS : KIND_STEP_FWD, stream);
 }
 
-int64_t kge_step_plan_size(int fn, int64_t nentity, int64_t ent_ld, int64_t nrelation, int64_t rel_ld,
-                           int64_t rel_off, int64_t B, int64_t N, int64_t D) {
-    if (fn < KGE_TRANSE || fn > KGE_PROTATE) return 0;
+// kge_step_plan_size / kge_step_plan over the descriptors (the planner calls them every step)
+static int64_t step_plan_bytes(const Tables& t, int64_t B, int64_t N) {
+    if (!valid_fn(t.fn)) return 0;
     ScoreParams tp;
-    const int R = planned_tile_params(fn, nentity, ent_ld, nrelation, rel_ld, rel_off, B, N, D, tp);
+    const int R = planned_tile_params(t, B, N, tp);
     return R ? plan_words(B, N, R) * 4 : 0;
 }
 
-int kge_step_plan(int fn, int mode, int64_t nentity, int64_t ent_ld, int64_t nrelation, int64_t rel_ld,
-                  int64_t rel_off, const int64_t* pos, const int64_t* neg, int64_t neg_ld, int64_t B, int64_t N,
-                  int64_t D, void* plan, void* stream) {
-    if (fn < KGE_TRANSE || fn > KGE_PROTATE) return fail(KGE_EINVAL, "unknown score function id " + std::to_string(fn));
-    if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH)
+int64_t kge_step_plan_size(int fn, int64_t nentity, int64_t ent_ld, int64_t nrelation, int64_t rel_ld,
+                           int64_t rel_off, int64_t B, int64_t N, int64_t D) {
+    return step_plan_bytes({fn, nullptr, nentity, ent_ld, nullptr, nrelation, rel_ld, rel_off, D, 0.f, 0.f, 0.f}, B, N);
+}
+
+static int step_plan(const Tables& t, const Batch& b, void* plan, void* stream) {
+    if (!valid_fn(t.fn)) return fail(KGE_EINVAL, "unknown score function id " + std::to_string(t.fn));
+    if (b.mode != KGE_HEAD_BATCH && b.mode != KGE_TAIL_BATCH)
         return fail(KGE_EINVAL, "kge_step_plan needs a negative mode (0 or 1)");
-    if (B <= 0 || N <= 0 || D <= 0) return fail(KGE_EINVAL, "bad shape (B, N, D)");
-    if (!pos || !neg || !plan) return fail(KGE_EINVAL, "null pointer");
+    if (b.B <= 0 || b.N <= 0 || t.D <= 0) return fail(KGE_EINVAL, "bad shape (B, N, D)");
+    if (!b.pos || !b.neg || !plan) return fail(KGE_EINVAL, "null pointer");
     if (!aligned(plan, 16)) return fail(KGE_EINVAL, "the plan must be 16-B aligned");
     ScoreParams tp;
-    if (!planned_tile_params(fn, nentity, ent_ld, nrelation, rel_ld, rel_off, B, N, D, tp))
+    if (!planned_tile_params(t, b.B, b.N, tp))
         return fail(KGE_ENOTSUP, "the tile form does not apply to this shape (kge_step_plan_size is 0)");
-    const PlanArgs a = plan_args(tp, mode, nentity, nrelation, pos, neg, neg_ld, B, N, plan);
-    const unsigned groups = (unsigned)plan_groups(B, tp.tile_rows);
+    const PlanArgs a = plan_args(tp, t, b, plan);
+    const unsigned groups = (unsigned)plan_groups(b.B, tp.tile_rows);
     if (tp.tile_waves == 16)
         hipLaunchKernelGGL(tile_plan_kernel<16>, dim3(groups), dim3(16 * kWave), plan_lds_ints(16 * kWave) * 4,
                            (hipStream_t)stream, a);
@@ -877,68 +915,59 @@ int kge_step_plan(int fn, int mode, int64_t nentity, int64_t ent_ld, int64_t nre
     return check_launch("kge_step_plan");
 }
 
-static int step_forward_planned(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
-                                int64_t nrelation, int64_t rel_ld, int64_t rel_off, int64_t B, int64_t N, int64_t D,
-                                float gamma, float emb_range, float modulus, float temperature, int adversarial,
-                                const void* plan, const int64_t* next_pos, const int64_t* next_neg,
-                                int64_t next_neg_ld, int next_mode, void* next_plan, float* neg_scores, int64_t ns_ld,
-                                float* out_neg, float* pos_scores, float* out_pos, int reverse, const SweepForm* sf,
-                                void* stream);
-
-int kge_step_forward_planned(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
-                             int64_t nrelation, int64_t rel_ld, int64_t rel_off, int64_t B, int64_t N, int64_t D,
-                             float gamma, float emb_range, float modulus, float temperature, int adversarial,
-                             const void* plan, const int64_t* next_pos, const int64_t* next_neg, int64_t next_neg_ld,
-                             int next_mode, void* next_plan, float* neg_scores, int64_t ns_ld, float* out_neg,
-                             float* pos_scores, float* out_pos, void* stream) {
-    return step_forward_planned(fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, B, N, D, gamma,
-                                emb_range, modulus, temperature, adversarial, plan, next_pos, next_neg, next_neg_ld,
-                                next_mode, next_plan, neg_scores, ns_ld, out_neg, pos_scores, out_pos, 0, nullptr,
-                                stream);
+int kge_step_plan(int fn, int mode, int64_t nentity, int64_t ent_ld, int64_t nrelation, int64_t rel_ld,
+                  int64_t rel_off, const int64_t* pos, const int64_t* neg, int64_t neg_ld, int64_t B, int64_t N,
+                  int64_t D, void* plan, void* stream) {
+    return step_plan({fn, nullptr, nentity, ent_ld, nullptr, nrelation, rel_ld, rel_off, D, 0.f, 0.f, 0.f},
+                     {mode, pos, neg, neg_ld, B, N}, plan, stream);
 }
 
-static int step_forward_planned(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
-                                int64_t nrelation, int64_t rel_ld, int64_t rel_off, int64_t B, int64_t N, int64_t D,
-                                float gamma, float emb_range, float modulus, float temperature, int adversarial,
-                                const void* plan, const int64_t* next_pos, const int64_t* next_neg,
-                                int64_t next_neg_ld, int next_mode, void* next_plan, float* neg_scores, int64_t ns_ld,
-                                float* out_neg, float* pos_scores, float* out_pos, int reverse, const SweepForm* sf,
+// the outputs of a step forward
+struct StepOut {
+    float* neg_scores;
+    int64_t ns_ld;
+    float *out_neg, *pos_scores, *out_pos;
+};
+
+// One planned step: batch b (its ids are the plan's: b.pos and b.neg are not read) scored from `plan`, the plan of
+// batch `next` made into next_plan (null: none). sf: the planner's sweep form (null: the library's).
+static int step_forward_planned(const Tables& t, const Batch& b, float temperature, int adversarial, const void* plan,
+                                const Batch& next, void* next_plan, const StepOut& o, const SweepForm* sf,
                                 void* stream) {
-    int rc = check_fn_mode(fn, mode);
+    int rc = check_fn_mode(t.fn, b.mode);
     if (rc) return rc;
-    if (mode == KGE_SINGLE) return fail(KGE_EINVAL, "kge_step_forward_planned needs a negative mode (0 or 1)");
-    if (B <= 0 || N <= 0 || D <= 0) return fail(KGE_EINVAL, "bad shape (B, N, D)");
-    if (!ent || !rel || !plan || !neg_scores || !out_neg || !out_pos) return fail(KGE_EINVAL, "null pointer");
+    if (b.mode == KGE_SINGLE) return fail(KGE_EINVAL, "kge_step_forward_planned needs a negative mode (0 or 1)");
+    if (b.B <= 0 || b.N <= 0 || t.D <= 0) return fail(KGE_EINVAL, "bad shape (B, N, D)");
+    if (!t.ent || !t.rel || !plan || !o.neg_scores || !o.out_neg || !o.out_pos) return fail(KGE_EINVAL, "null pointer");
     if (next_plan) {
-        if (next_mode != KGE_HEAD_BATCH && next_mode != KGE_TAIL_BATCH)
+        if (next.mode != KGE_HEAD_BATCH && next.mode != KGE_TAIL_BATCH)
             return fail(KGE_EINVAL, "the next batch needs a negative mode (0 or 1)");
-        if (!next_pos || !next_neg) return fail(KGE_EINVAL, "next_plan needs next_pos and next_neg");
+        if (!next.pos || !next.neg) return fail(KGE_EINVAL, "next_plan needs next_pos and next_neg");
         if (next_plan == plan) return fail(KGE_EINVAL, "next_plan must not be the plan this step reads");
         if (!aligned(next_plan, 16)) return fail(KGE_EINVAL, "the plan must be 16-B aligned");
     }
     if (!aligned(plan, 16)) return fail(KGE_EINVAL, "the plan must be 16-B aligned");
     ScoreParams tp;
-    const int R = planned_tile_params(fn, nentity, ent_ld, nrelation, rel_ld, rel_off, B, N, D, tp);
+    const int R = planned_tile_params(t, b.B, b.N, tp);
     ScoreParams p;
-    fill_indexed(p, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, nullptr, nullptr, 0, B, N, D,
-                 gamma, emb_range, modulus);
+    fill_indexed(p, t, {b.mode, nullptr, nullptr, 0, b.B, b.N});
     // the planner's sweep form: a plan does not depend on it (the same rows per group at every wave count)
     kge_forms fm = {-1, 0, 0, -1, sf ? sf->waves : 0, 0, 0};
-    if (!R || !tile_plan(fn, p, &fm) || p.tile_rows != R)
+    if (!R || !tile_plan(t.fn, p, &fm) || p.tile_rows != R)
         return fail(KGE_ENOTSUP, "the tile form does not apply to these tables (unaligned rows, or "
                                  "kge_step_plan_size is 0): use kge_step_forward");
-    p.out = neg_scores;
-    p.out_ld = ns_ld;
+    p.out = o.neg_scores;
+    p.out_ld = o.ns_ld;
     p.pos_base = nullptr;
     p.temperature = temperature;
     p.adversarial = adversarial;
-    p.out_neg = out_neg;
-    p.out_pos_raw = pos_scores;
-    p.out_pos_ls = out_pos;
+    p.out_neg = o.out_neg;
+    p.out_pos_raw = o.pos_scores;
+    p.out_pos_ls = o.out_pos;
     p.tile_pos = 1;
-    p.tile_rev = reverse;
     p.tile_plan = reinterpret_cast<const int*>(plan);
     if (sf) {
+        p.tile_rev = sf->rev;
         p.tile_depth = sf->depth;
         p.tile_board = sf->board;
         p.tile_tag = sf->tag;
@@ -949,25 +978,34 @@ static int step_forward_planned(int fn, int mode, const float* ent, int64_t nent
     // (C2 device time per step, alternating modes: 93.6 us; made beside the row reductions 99.5 us, as a launch
     // of its own 101.6 us, not planned 101.9 us; scripts/plan_probe.py, profiles/r05_plan_ab.txt)
     if (next_plan) {
-        p.tile_next = plan_args(tp, next_mode, nentity, nrelation, next_pos, next_neg, next_neg_ld, B, N, next_plan);
+        p.tile_next = plan_args(tp, t, next, next_plan);
         p.tile_lds = std::max(p.tile_lds, plan_lds_ints(p.tile_waves * kWave) * 4);
     }
-    rc = run_score(fn, mode, p, KIND_STEP_FWD_TILE, stream);
+    rc = run_score(t.fn, b.mode, p, KIND_STEP_FWD_TILE, stream);
     if (rc) return rc;
-    const int64_t blocks = (B + kWavesPerBlock - 1) / kWavesPerBlock;
-    hipLaunchKernelGGL(neg_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, p);
-    return check_launch("kge_step_forward_planned row reductions");
+    return launch_neg_rows(p, "kge_step_forward_planned row reductions", stream);
+}
+
+int kge_step_forward_planned(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
+                             int64_t nrelation, int64_t rel_ld, int64_t rel_off, int64_t B, int64_t N, int64_t D,
+                             float gamma, float emb_range, float modulus, float temperature, int adversarial,
+                             const void* plan, const int64_t* next_pos, const int64_t* next_neg, int64_t next_neg_ld,
+                             int next_mode, void* next_plan, float* neg_scores, int64_t ns_ld, float* out_neg,
+                             float* pos_scores, float* out_pos, void* stream) {
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
+    return step_forward_planned(t, {mode, nullptr, nullptr, 0, B, N}, temperature, adversarial, plan,
+                                {next_mode, next_pos, next_neg, next_neg_ld, B, N}, next_plan,
+                                {neg_scores, ns_ld, out_neg, pos_scores, out_pos}, nullptr, stream);
 }
 
 // The planned step loop as a handle (kge_step_planner_*): the tables, shapes and the two plan buffers are given
 // once; a step then passes only the next batch and the outputs (9 arguments instead of 29: at C2 the device
 // step is ~93 us and the host issues one step per step, so its per-call cost is part of the loop's rate).
 struct kge_step_planner {
-    int fn = 0, adversarial = 1;
-    const float* ent = nullptr;
-    const float* rel = nullptr;
-    int64_t nentity = 0, ent_ld = 0, nrelation = 0, rel_ld = 0, rel_off = 0, B = 0, N = 0, D = 0;
-    float gamma = 0.f, emb_range = 0.f, modulus = 0.f, temperature = 1.f;
+    Tables t = {};
+    int64_t B = 0, N = 0;
+    float temperature = 1.f;
+    int adversarial = 1;
     void* plans[2] = {nullptr, nullptr};
     int cur = -1;  // the buffer holding the next step's plan (-1: none)
     int mode = 0;  // that plan's batch mode
@@ -987,8 +1025,8 @@ struct kge_step_planner {
 
 // what the planner's next step runs (the setters' choices over the library's), and whether its throttle runs
 static SweepForm planner_form(const kge_step_planner* sp) {
-    SweepForm f = {0, 0, 0, 0, nullptr, sp->clk};
-    planned_sweep_defaults(sp->fn, sp->D, f.waves, f.depth, f.lead);
+    SweepForm f = {0, 0, 0, 0, sp->sweep ? (int)(sp->steps & 1) : 0, nullptr, sp->clk};
+    planned_sweep_defaults(sp->t.fn, sp->t.D, f.waves, f.depth, f.lead);
     if (sp->waves) f.waves = sp->waves;
     if (sp->depth) f.depth = sp->depth;
     if (f.waves == 8) f.depth = 2;
@@ -1004,33 +1042,23 @@ int kge_step_planner_create(kge_step_planner** out, int fn, const float* ent, in
                             void* plan0, void* plan1, int64_t plan_bytes, void* stream) {
     if (!out) return fail(KGE_EINVAL, "kge_step_planner_create: null pointer");
     *out = nullptr;
-    const int64_t need = kge_step_plan_size(fn, nentity, ent_ld, nrelation, rel_ld, rel_off, B, N, D);
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
+    const int64_t need = step_plan_bytes(t, B, N);
     if (need <= 0) return fail(KGE_ENOTSUP, "kge_step_planner_create: the tile form does not apply to this shape");
     if (!ent || !rel || !plan0 || !plan1 || plan0 == plan1) return fail(KGE_EINVAL, "kge_step_planner_create: bad pointers");
     if (plan_bytes < need || !aligned(plan0, 16) || !aligned(plan1, 16))
         return fail(KGE_EINVAL, "kge_step_planner_create: plan buffers too small or not 16-B aligned");
     kge_step_planner* sp = new kge_step_planner;
-    sp->fn = fn;
-    sp->ent = ent;
-    sp->nentity = nentity;
-    sp->ent_ld = ent_ld;
-    sp->rel = rel;
-    sp->nrelation = nrelation;
-    sp->rel_ld = rel_ld;
-    sp->rel_off = rel_off;
+    sp->t = t;
     sp->B = B;
     sp->N = N;
-    sp->D = D;
-    sp->gamma = gamma;
-    sp->emb_range = emb_range;
-    sp->modulus = modulus;
     sp->temperature = temperature;
     sp->adversarial = adversarial;
     sp->plans[0] = plan0;
     sp->plans[1] = plan1;
     sp->stream = stream;
     ScoreParams tp;
-    sp->groups = plan_groups(B, planned_tile_params(fn, nentity, ent_ld, nrelation, rel_ld, rel_off, B, N, D, tp));
+    sp->groups = plan_groups(B, planned_tile_params(t, B, N, tp));
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&sp->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -1046,10 +1074,7 @@ int kge_step_planner_set_form(kge_step_planner* sp, int waves, int depth) {
     if (waves) {  // the plans are made for the library's rows per group: the chosen block must take the same
         ScoreParams tp, tw;
         kge_forms fm = {-1, 0, 0, -1, waves, 0, 0};
-        if (planned_tile_params(sp->fn, sp->nentity, sp->ent_ld, sp->nrelation, sp->rel_ld, sp->rel_off, sp->B, sp->N, sp->D,
-                                tw, &fm) !=
-            planned_tile_params(sp->fn, sp->nentity, sp->ent_ld, sp->nrelation, sp->rel_ld, sp->rel_off, sp->B, sp->N, sp->D,
-                                tp))
+        if (planned_tile_params(sp->t, sp->B, sp->N, tw, &fm) != planned_tile_params(sp->t, sp->B, sp->N, tp))
             return fail(KGE_ENOTSUP, "kge_step_planner_set_form: this wave count changes the rows per group");
     }
     sp->waves = waves;
@@ -1104,7 +1129,7 @@ int kge_step_planner_set_clocks(kge_step_planner* sp, void* clocks, int64_t cloc
 
 int kge_step_planner_set_modulus(kge_step_planner* sp, float modulus) {
     if (!sp) return fail(KGE_EINVAL, "kge_step_planner_set_modulus: null pointer");
-    sp->modulus = modulus;
+    sp->t.modulus = modulus;
     return ok();
 }
 
@@ -1118,8 +1143,7 @@ int kge_step_planner_set_sweep(kge_step_planner* sp, int alternate) {
 int kge_step_planner_plan(kge_step_planner* sp, const int64_t* pos, const int64_t* neg, int64_t neg_ld, int mode) {
     if (!sp) return fail(KGE_EINVAL, "kge_step_planner_plan: null pointer");
     const int buf = sp->cur < 0 ? 0 : sp->cur;
-    const int rc = kge_step_plan(sp->fn, mode, sp->nentity, sp->ent_ld, sp->nrelation, sp->rel_ld, sp->rel_off, pos, neg,
-                                 neg_ld, sp->B, sp->N, sp->D, sp->plans[buf], sp->stream);
+    const int rc = step_plan(sp->t, {mode, pos, neg, neg_ld, sp->B, sp->N}, sp->plans[buf], sp->stream);
     if (rc) return rc;
     sp->cur = buf;
     sp->mode = mode;
@@ -1132,11 +1156,11 @@ int kge_step_planner_step(kge_step_planner* sp, const int64_t* next_pos, const i
     if (sp->cur < 0) return fail(KGE_EINVAL, "kge_step_planner_step: no batch planned (kge_step_planner_plan first)");
     const bool nxt = next_pos && next_neg;
     const SweepForm sf = planner_form(sp);
-    const int rc = step_forward_planned(
-        sp->fn, sp->mode, sp->ent, sp->nentity, sp->ent_ld, sp->rel, sp->nrelation, sp->rel_ld, sp->rel_off, sp->B,
-        sp->N, sp->D, sp->gamma, sp->emb_range, sp->modulus, sp->temperature, sp->adversarial, sp->plans[sp->cur],
-        next_pos, next_neg, next_neg_ld, next_mode, nxt ? sp->plans[1 - sp->cur] : nullptr, neg_scores, sp->N, out_neg,
-        pos_scores, out_pos, sp->sweep ? (int)(sp->steps & 1) : 0, &sf, sp->stream);
+    const int rc = step_forward_planned(sp->t, {sp->mode, nullptr, nullptr, 0, sp->B, sp->N}, sp->temperature,
+                                        sp->adversarial, sp->plans[sp->cur],
+                                        {next_mode, next_pos, next_neg, next_neg_ld, sp->B, sp->N},
+                                        nxt ? sp->plans[1 - sp->cur] : nullptr,
+                                        {neg_scores, sp->N, out_neg, pos_scores, out_pos}, &sf, sp->stream);
     if (rc) return rc;
     ++sp->steps;
     if (nxt) {
@@ -1164,9 +1188,9 @@ int kge_score_sharded(int fn, int mode, const float* qent, int64_t q_ld, const f
     if (empty(B, mode == KGE_SINGLE ? 1 : N)) return ok();
     if (!pos || (mode != KGE_SINGLE && !neg) || !scores || !qent || !shard)
         return fail(KGE_EINVAL, "null pointer");
+    const Tables t = {fn, shard, shard_rows, shard_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
     ScoreParams p;
-    fill_indexed(p, fn, mode, shard, shard_rows, shard_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N,
-                 D, gamma, emb_range, modulus);
+    fill_indexed(p, t, {mode, pos, neg, neg_ld, B, N});
     // query entity rows come pre-assembled (row b of qent); candidates from the local shard
     p.qent = qent;
     p.q_idx = nullptr;
@@ -1201,9 +1225,9 @@ int kge_shard_score(int fn, int mode, const float* qent, int64_t q_rows, int64_t
     if (B == 0) return ok();
     if (!pos || !send || !qent || !q_idx || !shard || !bucket || !bucket_start || !pre || !cnt || !tot)
         return fail(KGE_EINVAL, "null pointer");
+    const Tables t = {fn, shard, shard_rows, shard_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
     ScoreParams p;
-    fill_indexed(p, fn, mode, shard, shard_rows, shard_ld, rel, nrelation, rel_ld, rel_off, pos, nullptr, 0, B, N + 1,
-                 D, gamma, emb_range, modulus);
+    fill_indexed(p, t, {mode, pos, nullptr, 0, B, N + 1});
     // query entity rows: row q_idx[b] of the exchanged query block; candidates: the bucket's shard rows
     p.qent = qent;
     p.q_idx = q_idx;
@@ -1253,8 +1277,8 @@ int kge_eval_query(int fn, int mode, const float* ent, int64_t nentity, int64_t 
     if (B == 0) return ok();
     if (!ent || !rel || !pos || !Q) return fail(KGE_EINVAL, "null pointer");
     ScoreParams p;
-    fill_indexed(p, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, 0, pos, nullptr, 0, B, 1, D, 0.f, 1.f,
-                 0.f);
+    fill_indexed(p, {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, 0, D, 0.f, 1.f, 0.f},
+                 {mode, pos, nullptr, 0, B, 1});
     int V = 1, G = 1;
     rc = pick_vg(p, V, G);
     if (rc) return rc;
@@ -1282,8 +1306,8 @@ int kge_eval_query_planes(int fn, int mode, const float* ent, int64_t nentity, i
     if (!ent || !rel || !pos || !planes) return fail(KGE_EINVAL, "null pointer");
     if (!aligned(planes, 16)) return fail(KGE_EINVAL, "kge_eval_query_planes: planes not 16-B aligned");
     ScoreParams p;
-    fill_indexed(p, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, 0, pos, nullptr, 0, B, 1, D, 0.f, 1.f,
-                 0.f);
+    fill_indexed(p, {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, 0, D, 0.f, 1.f, 0.f},
+                 {mode, pos, nullptr, 0, B, 1});
     int V = 1, G = 1;
     rc = pick_vg(p, V, G);
     if (rc) return rc;
@@ -1609,9 +1633,9 @@ int kge_score_indexed_bwd(int fn, int mode, const float* ent, int64_t nentity, i
     if (!pos) return fail(KGE_EINVAL, "pos must not be NULL");
     if (mode != KGE_SINGLE && !neg) return fail(KGE_EINVAL, "neg must not be NULL in head/tail-batch mode");
     if (!d_scores || !d_ent || !d_rel) return fail(KGE_EINVAL, "null gradient pointer");
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
     ScoreParams p;
-    fill_indexed(p, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N, D, gamma,
-                 emb_range, modulus);
+    fill_indexed(p, t, {mode, pos, neg, neg_ld, B, N});
     p.d_scores = d_scores;
     p.d_ld = d_ld;
     p.d_qent = d_ent;
@@ -1622,7 +1646,7 @@ int kge_score_indexed_bwd(int fn, int mode, const float* ent, int64_t nentity, i
 }
 
 int64_t kge_step_backward_workspace_size(int fn, int64_t nentity, int64_t B, int64_t N, int64_t D) {
-    if (fn < KGE_TRANSE || fn > KGE_PROTATE || nentity < 0 || B < 0 || N < 0 || D <= 0) return -1;
+    if (!valid_fn(fn) || nentity < 0 || B < 0 || N < 0 || D <= 0) return -1;
     return step_ws_layout(nullptr, nentity, B, N, D, ent_width(fn, D), rel_width(fn, D)).bytes;
 }
 
@@ -1635,17 +1659,16 @@ struct StepOpts {
     float *rel_p = nullptr, *rel_m = nullptr, *rel_v = nullptr;  // Adam on the relation table, fused
 };
 
-static EvArgs ev_args(const int64_t* pos, const int64_t* neg, int64_t neg_ld, int64_t B, int64_t N, int64_t E,
-                      int mode) {
+static EvArgs ev_args(const Batch& b, int64_t E) {
     EvArgs a;
-    a.pos = pos;
-    a.neg = neg;
-    a.neg_ld = neg_ld;
-    a.B = B;
-    a.N = N;
+    a.pos = b.pos;
+    a.neg = b.neg;
+    a.neg_ld = b.neg_ld;
+    a.B = b.B;
+    a.N = b.N;
     a.E = E;
-    a.qcol = mode == KGE_HEAD_BATCH ? 2 : 0;
-    a.total = (int)(B * N + 3 * B);
+    a.qcol = b.mode == KGE_HEAD_BATCH ? 2 : 0;
+    a.total = (int)(b.B * b.N + 3 * b.B);
     return a;
 }
 
@@ -1661,39 +1684,53 @@ static int launch_events(const EvArgs& a, const StepWs& w, hipStream_t st) {
     return check_launch("kge_step_backward events");
 }
 
-static int step_backward_impl(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
-                              int64_t nrelation, int64_t rel_ld, int64_t rel_off, const int64_t* pos,
-                              const int64_t* neg, int64_t neg_ld, int64_t B, int64_t N, int64_t D, float gamma,
-                              float emb_range, float modulus, float temperature, int adversarial, int detach,
-                              const float* neg_scores, int64_t ns_ld, const float* pos_scores, const float* d_out_neg,
-                              const float* d_out_pos, float* d_ent, float* d_rel, float* d_modulus,
-                              const float* cand_stats, void* workspace, int64_t workspace_bytes, void* stream,
-                              const AdamArgs* adam, float* m_ent, float* v_ent, const StepOpts& o = StepOpts()) {
+// the streaming forms of the backward (KIND_BWD_STREAM, KIND_BWD_ENT_STREAM): every wave of the block owns whole
+// column groups
+static bool stream_form(int G) { return G >= kWavesPerBlock && G % kWavesPerBlock == 0 && G <= kMaxG; }
+
+static void set_adam(ScoreParams& p, const AdamArgs& a, float* m, float* v) {
+    p.adam.on = 1;
+    p.adam.m = m;
+    p.adam.v = v;
+    p.adam.b1 = a.b1;
+    p.adam.b2 = a.b2;
+    p.adam.eps = a.eps;
+    p.adam.alpha = a.alpha;
+    p.adam.step_size = a.step_size;
+    p.adam.bc2_sqrt = a.bc2_sqrt;
+    p.adam.keras = a.keras;
+}
+
+static int step_backward_impl(const Tables& t, const Batch& b, const StepGrads& g, void* workspace,
+                              int64_t workspace_bytes, void* stream, const AdamArgs* adam, float* m_ent, float* v_ent,
+                              const StepOpts& o = StepOpts()) {
+    const int fn = t.fn, mode = b.mode;
+    const int64_t B = b.B, N = b.N;
     int rc = check_fn_mode(fn, mode);
     if (rc) return rc;
     if (mode == KGE_SINGLE) return fail(KGE_EINVAL, "kge_step_backward needs a negative mode (0 or 1)");
-    if (B < 0 || N <= 0 || D <= 0 || nentity < 0 || nrelation < 0) return fail(KGE_EINVAL, "bad shape");
-    if (!ent || !rel || !pos || !neg || !neg_scores || !pos_scores || !d_out_neg || !d_out_pos || !d_rel ||
-        (!adam && !d_ent) || (adam && (!m_ent || !v_ent)))
+    if (B < 0 || N <= 0 || t.D <= 0 || t.nentity < 0 || t.nrelation < 0) return fail(KGE_EINVAL, "bad shape");
+    if (!t.ent || !t.rel || !b.pos || !b.neg || !g.neg_scores || !g.pos_scores || !g.d_out_neg || !g.d_out_pos ||
+        !g.d_rel || (!adam && !g.d_ent) || (adam && (!m_ent || !v_ent)))
         return fail(KGE_EINVAL, "null pointer");
-    if (B * N + 3 * B >= (int64_t)INT32_MAX || nentity >= (int64_t)INT32_MAX)
+    if (B * N + 3 * B >= (int64_t)INT32_MAX || t.nentity >= (int64_t)INT32_MAX)
         return fail(KGE_EINVAL, "too many gradient events for 32-bit codes");
-    const int64_t ent_w = ent_width(fn, D), rel_w = rel_width(fn, D);
+    const int64_t ent_w = ent_width(fn, t.D), rel_w = rel_width(fn, t.D);
     // relation rows are written over the table's width (the parts no score function reads get a zero
     // gradient), never over the padding of a row stride wider than the table
-    const int64_t rel_dim = rel_table_width(fn, D, rel_off, rel_ld);
-    StepWs w = step_ws_layout((char*)workspace, nentity, B, N, D, ent_w, rel_w);
+    const int64_t rel_dim = rel_table_width(fn, t.D, t.rel_off, t.rel_ld);
+    StepWs w = step_ws_layout((char*)workspace, t.nentity, B, N, t.D, ent_w, rel_w);
     if (!workspace || workspace_bytes < w.bytes) return fail(KGE_EINVAL, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     if (B == 0 && !adam) {
         // the tables' columns only: the last row of a padded buffer may end at its width
-        if ((nentity > 0 && hipMemset2DAsync(d_ent, (size_t)(ent_ld * 4), 0, (size_t)(ent_w * 4), (size_t)nentity,
-                                             st) != hipSuccess) ||
-            (nrelation > 0 && rel_dim > 0 &&
-             hipMemset2DAsync(d_rel, (size_t)(rel_ld * 4), 0, (size_t)(rel_dim * 4), (size_t)nrelation, st) !=
+        if ((t.nentity > 0 && hipMemset2DAsync(g.d_ent, (size_t)(t.ent_ld * 4), 0, (size_t)(ent_w * 4),
+                                               (size_t)t.nentity, st) != hipSuccess) ||
+            (t.nrelation > 0 && rel_dim > 0 &&
+             hipMemset2DAsync(g.d_rel, (size_t)(t.rel_ld * 4), 0, (size_t)(rel_dim * 4), (size_t)t.nrelation, st) !=
                  hipSuccess))
             return check_launch("kge_step_backward memset");
-        if (d_modulus && hipMemsetAsync(d_modulus, 0, 4, st) != hipSuccess) return check_launch("memset");
+        if (g.d_modulus && hipMemsetAsync(g.d_modulus, 0, 4, st) != hipSuccess) return check_launch("memset");
         return ok();
     }
     // 1. loss -> score gradients
@@ -1701,20 +1738,20 @@ static int step_backward_impl(int fn, int mode, const float* ent, int64_t nentit
         rc = 0;
     } else if (o.fused_dscores) {
         const unsigned nb = (unsigned)((B + kWavesPerBlock - 1) / kWavesPerBlock);
-        hipLaunchKernelGGL(neg_reduce_bwd_kernel, dim3(nb), dim3(kBlock), 0, st, neg_scores, B, N, ns_ld,
-                           temperature, adversarial, detach, d_out_neg, w.d_ns, N, pos_scores, d_out_pos, w.d_ps);
+        hipLaunchKernelGGL(neg_reduce_bwd_kernel, dim3(nb), dim3(kBlock), 0, st, g.neg_scores, B, N, g.ns_ld,
+                           g.temperature, g.adversarial, g.detach, g.d_out_neg, w.d_ns, N, g.pos_scores, g.d_out_pos,
+                           w.d_ps);
         rc = check_launch("kge_step_backward score gradients");
     } else {
-        rc = kge_neg_reduce_bwd(neg_scores, B, N, ns_ld, temperature, adversarial, detach, d_out_neg, w.d_ns, N,
-                                stream);
+        rc = kge_neg_reduce_bwd(g.neg_scores, B, N, g.ns_ld, g.temperature, g.adversarial, g.detach, g.d_out_neg,
+                                w.d_ns, N, stream);
         if (rc) return rc;
-        rc = kge_log_sigmoid_bwd(pos_scores, d_out_pos, B, w.d_ps, stream);
+        rc = kge_log_sigmoid_bwd(g.pos_scores, g.d_out_pos, B, w.d_ps, stream);
     }
     if (rc) return rc;
     // 2. phase 1: per-slot query gradients (negative call, then positive call)
     ScoreParams p;
-    fill_indexed(p, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N, D, gamma,
-                 emb_range, modulus);
+    fill_indexed(p, t, b);
     p.d_scores = w.d_ns;
     p.d_ld = N;
     p.qbuf = w.qbuf;
@@ -1734,10 +1771,10 @@ static int step_backward_impl(int fn, int mode, const float* ent, int64_t nentit
     } else if (o.dq_ready) {
         // the fused forward (KIND_STEP_FWD_GRAD) left each row's query gradient, unscaled, in dqbuf
         p.dqbuf = w.dqbuf;
-        p.dq_scale = d_out_neg;
+        p.dq_scale = g.d_out_neg;
         rc = run_score(fn, mode, p, KIND_BWD_CHAIN, stream);
-    } else if (G1 >= kWavesPerBlock && G1 % kWavesPerBlock == 0 && G1 <= kMaxG && (fn != KGE_INTERHT || cand_stats)) {
-        p.cand_stats = reinterpret_cast<float2*>(const_cast<float*>(cand_stats));
+    } else if (stream_form(G1) && (fn != KGE_INTERHT || g.cand_stats)) {
+        p.cand_stats = reinterpret_cast<float2*>(const_cast<float*>(g.cand_stats));
         p.dqbuf = w.dqbuf;
         rc = run_score(fn, mode, p, KIND_BWD_STREAM, stream);
         if (rc) return rc;
@@ -1747,8 +1784,7 @@ static int step_backward_impl(int fn, int mode, const float* ent, int64_t nentit
     }
     if (rc) return rc;
     ScoreParams pp;
-    fill_indexed(pp, fn, KGE_SINGLE, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, nullptr, 0, B, 1, D,
-                 gamma, emb_range, modulus);
+    fill_indexed(pp, t, single_of(b));
     pp.d_scores = w.d_ps;
     pp.d_ld = 1;
     pp.qbuf = w.qbuf;
@@ -1764,13 +1800,12 @@ static int step_backward_impl(int fn, int mode, const float* ent, int64_t nentit
     }
     // 3. bucket the gradient events by entity
     if (!o.events_ready) {
-        rc = launch_events(ev_args(pos, neg, neg_ld, B, N, nentity, mode), w, st);
+        rc = launch_events(ev_args(b, t.nentity), w, st);
         if (rc) return rc;
     }
     // 4. phase 2: one wave per entity row, events in code order -> every row of d_ent written
     ScoreParams q;
-    fill_indexed(q, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N, D, gamma,
-                 emb_range, modulus);
+    fill_indexed(q, t, b);
     q.qbuf = w.qbuf;
     q.qg_ent = w.qg_ent;
     q.ev_off = w.off;
@@ -1780,28 +1815,16 @@ static int step_backward_impl(int fn, int mode, const float* ent, int64_t nentit
     q.Bn = B;
     q.Nn = N;
     q.ent_w = ent_w;
-    q.d_out_ent = d_ent;
-    if (adam) {
-        q.adam.on = 1;
-        q.adam.m = m_ent;
-        q.adam.v = v_ent;
-        q.adam.b1 = adam->b1;
-        q.adam.b2 = adam->b2;
-        q.adam.eps = adam->eps;
-        q.adam.alpha = adam->alpha;
-        q.adam.step_size = adam->step_size;
-        q.adam.bc2_sqrt = adam->bc2_sqrt;
-        q.adam.keras = adam->keras;
-    }
-    if (nentity > 0) {
+    q.d_out_ent = g.d_ent;
+    if (adam) set_adam(q, *adam, m_ent, v_ent);
+    if (t.nentity > 0) {
         // streaming form (block per row, waves split the columns) under the same condition as phase 1
-        const bool ent_stream = G1 >= kWavesPerBlock && G1 % kWavesPerBlock == 0 && G1 <= kMaxG;
-        rc = run_score(fn, mode, q, ent_stream ? KIND_BWD_ENT_STREAM : KIND_BWD_ENT, stream);
+        rc = run_score(fn, mode, q, stream_form(G1) ? KIND_BWD_ENT_STREAM : KIND_BWD_ENT, stream);
         if (rc) return rc;
     }
     // 5. relation rows (slot order) and the pRotatE modulus
-    if (nrelation > 0 || d_modulus) {
-        const int64_t rb = std::max<int64_t>(1, nrelation * ((rel_dim + kWave - 1) / kWave));
+    if (t.nrelation > 0 || g.d_modulus) {
+        const int64_t rb = std::max<int64_t>(1, t.nrelation * ((rel_dim + kWave - 1) / kWave));
         RelAdam ra;
         memset(&ra, 0, sizeof(ra));
         if (adam && o.rel_p) {
@@ -1811,8 +1834,8 @@ static int step_backward_impl(int fn, int mode, const float* ent, int64_t nentit
             ra.a = *adam;
             ra.on = 1;
         }
-        hipLaunchKernelGGL(bwd_rel_kernel, dim3((unsigned)rb), dim3(kRelWaves * kWave), 0, st, pos, B, nrelation, w.qg_rel, rel_w,
-                           rel_off, d_rel, rel_ld, rel_dim, w.dmod, d_modulus, ra);
+        hipLaunchKernelGGL(bwd_rel_kernel, dim3((unsigned)rb), dim3(kRelWaves * kWave), 0, st, b.pos, B, t.nrelation,
+                           w.qg_rel, rel_w, t.rel_off, g.d_rel, t.rel_ld, rel_dim, w.dmod, g.d_modulus, ra);
     }
     return check_launch("kge_step_backward");
 }
@@ -1824,10 +1847,11 @@ int kge_step_backward(int fn, int mode, const float* ent, int64_t nentity, int64
                       const float* pos_scores, const float* d_out_neg, const float* d_out_pos, float* d_ent,
                       float* d_rel, float* d_modulus, const float* cand_stats, void* workspace,
                       int64_t workspace_bytes, void* stream) {
-    return step_backward_impl(fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N,
-                              D, gamma, emb_range, modulus, temperature, adversarial, detach, neg_scores, ns_ld,
-                              pos_scores, d_out_neg, d_out_pos, d_ent, d_rel, d_modulus, cand_stats, workspace,
-                              workspace_bytes, stream, nullptr, nullptr, nullptr);
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
+    const StepGrads g = {temperature, adversarial, detach, neg_scores, ns_ld,    pos_scores,
+                         d_out_neg,   d_out_pos,   d_ent,  d_rel,      d_modulus, cand_stats};
+    return step_backward_impl(t, {mode, pos, neg, neg_ld, B, N}, g, workspace, workspace_bytes, stream, nullptr,
+                              nullptr, nullptr);
 }
 
 // Adam coefficients of step t (1-based), in double on the host
@@ -1875,10 +1899,10 @@ int kge_step_backward_adam(int fn, int mode, float* ent, int64_t nentity, int64_
     o.rel_p = rel;  // Adam on the relation table inside the relation-gradient kernel
     o.rel_m = m_rel;
     o.rel_v = v_rel;
-    int rc = step_backward_impl(fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B,
-                                N, D, gamma, emb_range, modulus, temperature, adversarial, detach, neg_scores, ns_ld,
-                                pos_scores, d_out_neg, d_out_pos, nullptr, d_rel, modulus_param ? d_mod : nullptr,
-                                cand_stats, workspace, base, stream, &a, m_ent, v_ent, o);
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
+    const StepGrads g = {temperature, adversarial, detach,  neg_scores, ns_ld,                           pos_scores,
+                         d_out_neg,   d_out_pos,   nullptr, d_rel,      modulus_param ? d_mod : nullptr, cand_stats};
+    int rc = step_backward_impl(t, {mode, pos, neg, neg_ld, B, N}, g, workspace, base, stream, &a, m_ent, v_ent, o);
     if (rc) return rc;
     // the pRotatE modulus (one element) goes through the dense optimizer kernel, with the same
     // adam_update as the fused rows
@@ -1955,9 +1979,13 @@ int kge_train_step(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld
 
     // 1. forward of both model calls (supervisor.py:17-18); phase 1 of the backward fused in where its
     //    accumulators fit, and the gradient events counted into their entity buckets
+    const Tables tab = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, 0.f};
+    const Batch batch = {mode, pos, neg, neg_ld, B, N};
+    // the backward's loss side: the forward's scores and the loss kernel's (or the epilogue's) gradients, in the
+    // workspace; Adam is fused, so no gradient table but the relation's
+    StepGrads g = {temperature, adversarial, detach, t.ns, N, t.ps, t.d_out, t.d_out, nullptr, d_rel, nullptr, nullptr};
     ScoreParams p;
-    fill_indexed(p, fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N, D, gamma,
-                 emb_range, 0.f);
+    fill_indexed(p, tab, batch);
     p.out = t.ns;
     p.out_ld = N;
     p.pos_base = pos;
@@ -1983,10 +2011,8 @@ int kge_train_step(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld
         if (loss_sum) hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(1), 0, st, loss, loss_sum);
         rc = check_launch("kge_train_step loss");
         if (rc) return rc;
-        return step_backward_impl(fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B,
-                                  N, D, gamma, emb_range, 0.f, temperature, adversarial, detach, t.ns, N, t.ps,
-                                  t.d_out, t.d_out, nullptr, d_rel, nullptr, t.stats, workspace, base, stream, &a,
-                                  m_ent, v_ent, o);
+        g.cand_stats = t.stats;
+        return step_backward_impl(tab, batch, g, workspace, base, stream, &a, m_ent, v_ent, o);
     }
     // the per-entity event counters are zeroed here, on every call: the workspace carries no state
     // between calls, so any workspace contents (fresh, shared, or left by an aborted call) are valid. The
@@ -2036,9 +2062,7 @@ int kge_train_step(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld
     if (rc) return rc;
     // 4. phase 2 with Adam fused into the entity pass, relation gradient with Adam (supervisor.py:25-26)
     o.dq_ready = o.epilogue_done = true;
-    return step_backward_impl(fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N,
-                              D, gamma, emb_range, 0.f, temperature, adversarial, detach, t.ns, N, t.ps, t.d_out,
-                              t.d_out, nullptr, d_rel, nullptr, nullptr, workspace, base, stream, &a, m_ent, v_ent, o);
+    return step_backward_impl(tab, batch, g, workspace, base, stream, &a, m_ent, v_ent, o);
 }
 
 }  // extern "C"
@@ -2075,50 +2099,56 @@ static ShardWs shard_ws_layout(char* ws, int fn, int64_t rows, int64_t R, int64_
     return s;
 }
 
-static int shard_check(int fn, int mode, const float* shard, int64_t rows, const float* qent, const float* qent_pos,
-                       const float* rel, const int64_t* pos, const int64_t* neg, int64_t Bg, int64_t N, int64_t D,
-                       int64_t home_B, int world, int rank, const float* weight, void* ws, int64_t ws_bytes) {
-    int rc = check_fn_mode(fn, mode);
+// what the three calls of the sharded train step share beyond the tables (the shard is t.ent) and the batch
+struct ShardArgs {
+    int64_t shard_lo;
+    const float* qent;
+    const float* qent_pos;
+    int64_t q_ld, home_B;
+    int world, rank;
+    float temperature;
+    int adversarial, detach;
+    const float* weight;
+};
+
+static int shard_check(const Tables& t, const Batch& b, const ShardArgs& a, void* ws, int64_t ws_bytes) {
+    int rc = check_fn_mode(t.fn, b.mode);
     if (rc) return rc;
-    if (fn == KGE_PROTATE) return fail(KGE_ENOTSUP, "the sharded train step has no pRotatE modulus gradient");
-    if (mode == KGE_SINGLE) return fail(KGE_EINVAL, "the sharded train step needs a negative mode (0 or 1)");
-    if (Bg <= 0 || N <= 0 || D <= 0 || rows < 0 || world < 1 || rank < 0 || rank >= world || home_B <= 0 ||
-        home_B * world != Bg)
+    if (t.fn == KGE_PROTATE) return fail(KGE_ENOTSUP, "the sharded train step has no pRotatE modulus gradient");
+    if (b.mode == KGE_SINGLE) return fail(KGE_EINVAL, "the sharded train step needs a negative mode (0 or 1)");
+    if (b.B <= 0 || b.N <= 0 || t.D <= 0 || t.nentity < 0 || a.world < 1 || a.rank < 0 || a.rank >= a.world ||
+        a.home_B <= 0 || a.home_B * a.world != b.B)
         return fail(KGE_EINVAL, "bad shape: need Bg = world * home_B > 0, N, D > 0, 0 <= rank < world");
-    if (!shard || !qent || !qent_pos || !rel || !pos || !neg || !weight) return fail(KGE_EINVAL, "null pointer");
-    if (Bg * N + 3 * Bg >= (int64_t)INT32_MAX || rows >= (int64_t)INT32_MAX)
+    if (!t.ent || !a.qent || !a.qent_pos || !t.rel || !b.pos || !b.neg || !a.weight)
+        return fail(KGE_EINVAL, "null pointer");
+    if (b.B * b.N + 3 * b.B >= (int64_t)INT32_MAX || t.nentity >= (int64_t)INT32_MAX)
         return fail(KGE_EINVAL, "too many gradient events for 32-bit codes");
-    if (!ws || ws_bytes < shard_ws_layout(nullptr, fn, rows, 0, 0, Bg, N, D).bytes) return fail(KGE_EINVAL, "workspace too small");
+    if (!ws || ws_bytes < shard_ws_layout(nullptr, t.fn, t.nentity, 0, 0, b.B, b.N, t.D).bytes)
+        return fail(KGE_EINVAL, "workspace too small");
     return 0;
 }
 
-static void shard_params(ScoreParams& p, int fn, int mode, const float* shard, int64_t rows, int64_t ent_ld,
-                         int64_t shard_lo, const float* qent, const float* qent_pos, int64_t q_ld, const float* rel,
-                         int64_t nrelation, int64_t rel_ld, int64_t rel_off, const int64_t* pos, const int64_t* neg,
-                         int64_t neg_ld, int64_t Bg, int64_t N, int64_t D, int64_t home_B, int world, int rank,
-                         float gamma, float emb_range, float temperature, int adversarial, int detach,
-                         const float* weight, const ShardWs& w) {
-    fill_indexed(p, fn, mode, shard, rows, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, Bg, N, D, gamma,
-                 emb_range, 0.f);
-    p.qent = qent;  // row b: the negative call's query entity (assembled by the caller)
+static void shard_params(ScoreParams& p, const Tables& t, const Batch& b, const ShardArgs& a, const ShardWs& w) {
+    fill_indexed(p, t, b);
+    p.qent = a.qent;  // row b: the negative call's query entity (assembled by the caller)
     p.q_idx = nullptr;
-    p.q_ld = q_ld;
-    p.q_rows = Bg;
-    p.qent_pos = qent_pos;
-    p.c_base = shard_lo;
-    p.pos_base = pos;
-    p.temperature = temperature;
-    p.adversarial = adversarial;
-    p.detach = detach;
-    p.weight = weight;
-    p.home_B = home_B;
-    p.world = world;
-    p.rank = rank;
-    p.nq = shard_nq(fn);
+    p.q_ld = a.q_ld;
+    p.q_rows = b.B;
+    p.qent_pos = a.qent_pos;
+    p.c_base = a.shard_lo;
+    p.pos_base = b.pos;
+    p.temperature = a.temperature;
+    p.adversarial = a.adversarial;
+    p.detach = a.detach;
+    p.weight = a.weight;
+    p.home_B = a.home_B;
+    p.world = a.world;
+    p.rank = a.rank;
+    p.nq = shard_nq(t.fn);
     p.out = w.ns;
-    p.out_ld = N;
+    p.out_ld = b.N;
     p.neg_scores = w.ns;
-    p.ns_ld = N;
+    p.ns_ld = b.N;
     p.d_ns = w.step.d_ns;
     p.d_ps = w.step.d_ps;
     p.sh_A = w.A;
@@ -2128,13 +2158,11 @@ static void shard_params(ScoreParams& p, int fn, int mode, const float* shard, i
 
 extern "C" {
 
-int kge_shard_nq(int fn) { return (fn < KGE_TRANSE || fn > KGE_PROTATE) ? 0 : shard_nq(fn); }
+int kge_shard_nq(int fn) { return valid_fn(fn) ? shard_nq(fn) : 0; }
 
 int64_t kge_shard_train_workspace_size(int fn, int64_t shard_rows, int64_t nrelation, int64_t rel_ld, int64_t Bg,
                                        int64_t N, int64_t D) {
-    if (fn < KGE_TRANSE || fn > KGE_PROTATE || shard_rows < 0 || nrelation < 0 || rel_ld < 0 || Bg < 0 || N < 0 ||
-        D <= 0)
-        return -1;
+    if (!valid_fn(fn) || shard_rows < 0 || nrelation < 0 || rel_ld < 0 || Bg < 0 || N < 0 || D <= 0) return -1;
     return shard_ws_layout(nullptr, fn, shard_rows, nrelation, rel_ld, Bg, N, D).bytes;
 }
 
@@ -2144,8 +2172,10 @@ int kge_shard_train_forward(int fn, int mode, const float* shard, int64_t shard_
                             int64_t Bg, int64_t N, int64_t D, int64_t home_B, int world, int rank, float gamma,
                             float emb_range, float temperature, int adversarial, int detach, const float* weight,
                             float* stats, float* dq, void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = shard_check(fn, mode, shard, shard_rows, qent, qent_pos, rel, pos, neg, Bg, N, D, home_B, world, rank,
-                         weight, workspace, workspace_bytes);
+    const Tables t = {fn, shard, shard_rows, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, 0.f};
+    const Batch b = {mode, pos, neg, neg_ld, Bg, N};
+    const ShardArgs a = {shard_lo, qent, qent_pos, q_ld, home_B, world, rank, temperature, adversarial, detach, weight};
+    int rc = shard_check(t, b, a, workspace, workspace_bytes);
     if (rc) return rc;
     if (!stats || !dq) return fail(KGE_EINVAL, "null pointer");
     const ShardWs w = shard_ws_layout((char*)workspace, fn, shard_rows, nrelation, rel_ld, Bg, N, D);
@@ -2155,9 +2185,7 @@ int kge_shard_train_forward(int fn, int mode, const float* shard, int64_t shard_
     if (shard_rows > 0 && hipMemsetAsync(w.step.count, 0, (size_t)align256(shard_rows * 4), st) != hipSuccess)
         return check_launch("kge_shard_train_forward memset");
     ScoreParams p;
-    shard_params(p, fn, mode, shard, shard_rows, ent_ld, shard_lo, qent, qent_pos, q_ld, rel, nrelation, rel_ld,
-                 rel_off, pos, neg, neg_ld, Bg, N, D, home_B, world, rank, gamma, emb_range, temperature, adversarial,
-                 detach, weight, w);
+    shard_params(p, t, b, a, w);
     p.ev_count = w.step.count;
     p.sh_stats = stats;
     p.sh_dq = dq;
@@ -2174,16 +2202,16 @@ int kge_shard_train_combine(int fn, int mode, const float* shard, int64_t shard_
                             float emb_range, float temperature, int adversarial, int detach, const float* weight,
                             const float* stats_all, float* dq, float* out_neg, float* out_pos_raw, float* out_pos,
                             void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = shard_check(fn, mode, shard, shard_rows, qent, qent_pos, rel, pos, neg, Bg, N, D, home_B, world, rank,
-                         weight, workspace, workspace_bytes);
+    const Tables t = {fn, shard, shard_rows, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, 0.f};
+    const Batch b = {mode, pos, neg, neg_ld, Bg, N};
+    const ShardArgs a = {shard_lo, qent, qent_pos, q_ld, home_B, world, rank, temperature, adversarial, detach, weight};
+    int rc = shard_check(t, b, a, workspace, workspace_bytes);
     if (rc) return rc;
     if (!stats_all || !dq || !out_neg || !out_pos) return fail(KGE_EINVAL, "null pointer");
     const ShardWs w = shard_ws_layout((char*)workspace, fn, shard_rows, nrelation, rel_ld, Bg, N, D);
     if (workspace_bytes < w.bytes) return fail(KGE_EINVAL, "workspace too small");
     ScoreParams p;
-    shard_params(p, fn, mode, shard, shard_rows, ent_ld, shard_lo, qent, qent_pos, q_ld, rel, nrelation, rel_ld,
-                 rel_off, pos, neg, neg_ld, Bg, N, D, home_B, world, rank, gamma, emb_range, temperature, adversarial,
-                 detach, weight, w);
+    shard_params(p, t, b, a, w);
     p.sh_stats_all = stats_all;
     p.sh_dq = dq;
     p.out_neg = out_neg;
@@ -2202,8 +2230,10 @@ int kge_shard_train_backward(int fn, int mode, float* shard, int64_t shard_rows,
                              const float* dq, float* loss, float* loss_sum, float* m_ent, float* v_ent, float* m_rel,
                              float* v_rel, float lr, float beta1, float beta2, float eps, int64_t step, int keras,
                              void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = shard_check(fn, mode, shard, shard_rows, qent, qent_pos, rel, pos, neg, Bg, N, D, home_B, world, rank,
-                         weight, workspace, workspace_bytes);
+    const Tables t = {fn, shard, shard_rows, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, 0.f};
+    const Batch b = {mode, pos, neg, neg_ld, Bg, N};
+    const ShardArgs a = {shard_lo, qent, qent_pos, q_ld, home_B, world, rank, temperature, adversarial, detach, weight};
+    int rc = shard_check(t, b, a, workspace, workspace_bytes);
     if (rc) return rc;
     if (step < 1) return fail(KGE_EINVAL, "step is 1-based");
     if (!dq || !loss || !m_ent || !v_ent || !m_rel || !v_rel) return fail(KGE_EINVAL, "null pointer");
@@ -2217,9 +2247,7 @@ int kge_shard_train_backward(int fn, int mode, float* shard, int64_t shard_rows,
     rc = check_launch("kge_shard_train_backward scan");
     if (rc) return rc;
     ScoreParams e;
-    shard_params(e, fn, mode, shard, shard_rows, ent_ld, shard_lo, qent, qent_pos, q_ld, rel, nrelation, rel_ld,
-                 rel_off, pos, neg, neg_ld, Bg, N, D, home_B, world, rank, gamma, emb_range, temperature, adversarial,
-                 detach, weight, w);
+    shard_params(e, t, b, a, w);
     e.sh_dq = const_cast<float*>(dq);
     e.qbuf = w.step.qbuf;
     e.qg_ent = w.step.qg_ent;
@@ -2233,16 +2261,15 @@ int kge_shard_train_backward(int fn, int mode, float* shard, int64_t shard_rows,
     rc = run_score(fn, mode, e, KIND_SHARD_EPILOGUE, stream);
     if (rc) return rc;
     // phase 2 with Adam fused into the shard's rows, relation gradient with Adam (supervisor.py:25-26)
-    const AdamArgs a = adam_args(lr, beta1, beta2, eps, step, keras);
+    const AdamArgs adam = adam_args(lr, beta1, beta2, eps, step, keras);
     StepOpts o;
     o.dq_ready = o.epilogue_done = o.events_ready = true;
     o.rel_p = rel;
     o.rel_m = m_rel;
     o.rel_v = v_rel;
-    return step_backward_impl(fn, mode, shard, shard_rows, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld,
-                              Bg, N, D, gamma, emb_range, 0.f, temperature, adversarial, detach, w.ns, N, w.ns,
-                              w.step.d_ps, w.step.d_ps, nullptr, w.d_rel, nullptr, nullptr, workspace, w.base, stream,
-                              &a, m_ent, v_ent, o);
+    const StepGrads g = {temperature, adversarial, detach,  w.ns,    N,       w.ns,
+                         w.step.d_ps, w.step.d_ps, nullptr, w.d_rel, nullptr, nullptr};
+    return step_backward_impl(t, b, g, workspace, w.base, stream, &adam, m_ent, v_ent, o);
 }
 
 }  // extern "C"

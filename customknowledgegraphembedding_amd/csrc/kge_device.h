@@ -3554,34 +3554,34 @@ void launch_tile(const ScoreParams& p, hipStream_t st, int blocks) {
                        p);
 }
 
-template <int FN, bool CH, int V, int G>
-void launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
-    if (kind == KIND_SHARD_FWD_GRAD || kind == KIND_SHARD_POS || kind == KIND_SHARD_EPILOGUE)
-        launch_shard<FN, CH, V, G>(p, kind, st, blocks);
-    else if (kind == KIND_BWD)
-        hipLaunchKernelGGL((score_bwd_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    else if (kind == KIND_BWD_ROWS)
-        hipLaunchKernelGGL((bwd_rows_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    else if (kind == KIND_BWD_ENT)
-        hipLaunchKernelGGL((bwd_ent_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    else if (kind == KIND_BWD_STREAM) {
-        if constexpr (G % kWavesPerBlock == 0)
-            hipLaunchKernelGGL((bwd_stream_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    } else if (kind == KIND_BWD_ENT_STREAM) {
-        if constexpr (G % kWavesPerBlock == 0)
-            hipLaunchKernelGGL((bwd_ent_stream_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    } else if (kind == KIND_BWD_CHAIN)
-        hipLaunchKernelGGL((bwd_chain_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    else if (kind == KIND_FWD_STATS) {
-        if constexpr (FN == KGE_INTERHT)
-            hipLaunchKernelGGL((score_fwd_kernel<FN, CH, V, G, true>), dim3(blocks), dim3(kBlock), 0, st, p);
+// Launches kind `kind`; false when it has no (FN, CH, V, G) instantiation (nothing was launched). The guards are
+// kKinds' entries (kge_internal.h), the ones run_score checks.
+#define KGE_LAUNCH(kernel, ...) hipLaunchKernelGGL((kernel<__VA_ARGS__>), dim3(blocks), dim3(kBlock), 0, st, p)
+// the branch of a kind that is one kernel
+#define KGE_KIND(K, kernel, ...)                       \
+    if (kind == K) {                                   \
+        if constexpr (kind_has(K, FN, CH, G)) {        \
+            KGE_LAUNCH(kernel, __VA_ARGS__);           \
+            return true;                               \
+        }                                              \
+        return false;                                  \
     }
-    else if (kind == KIND_STEP_FWD)
-        hipLaunchKernelGGL((step_fwd_kernel<FN, CH, V, G, false>), dim3(blocks), dim3(kBlock), 0, st, p);
-    else if (kind == KIND_STEP_FWD_XCD)
-        hipLaunchKernelGGL((step_fwd_xcd_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    else if (kind == KIND_STEP_FWD_TILE || kind == KIND_SCORE_TILE) {
-        if constexpr (G <= kFwdGradMaxG) {
+template <int FN, bool CH, int V, int G>
+bool launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
+    if (kind == KIND_SHARD_FWD_GRAD || kind == KIND_SHARD_POS || kind == KIND_SHARD_EPILOGUE)
+        return launch_shard<FN, CH, V, G>(p, kind, st, blocks);
+    KGE_KIND(KIND_BWD, score_bwd_kernel, FN, CH, V, G)
+    KGE_KIND(KIND_BWD_ROWS, bwd_rows_kernel, FN, CH, V, G)
+    KGE_KIND(KIND_BWD_ENT, bwd_ent_kernel, FN, CH, V, G)
+    KGE_KIND(KIND_BWD_STREAM, bwd_stream_kernel, FN, CH, V, G)
+    KGE_KIND(KIND_BWD_ENT_STREAM, bwd_ent_stream_kernel, FN, CH, V, G)
+    KGE_KIND(KIND_BWD_CHAIN, bwd_chain_kernel, FN, CH, V, G)
+    KGE_KIND(KIND_FWD_STATS, score_fwd_kernel, FN, CH, V, G, true)
+    KGE_KIND(KIND_STEP_FWD, step_fwd_kernel, FN, CH, V, G, false)
+    KGE_KIND(KIND_STEP_FWD_XCD, step_fwd_xcd_kernel, FN, CH, V, G)
+    if (kind == KIND_STEP_FWD_TILE || kind == KIND_SCORE_TILE) {
+        static_assert(kind_has(KIND_STEP_FWD_TILE, FN, CH, G) == kind_has(KIND_SCORE_TILE, FN, CH, G), "one kernel");
+        if constexpr (kind_has(KIND_STEP_FWD_TILE, FN, CH, G)) {
             // (waves, candidate rows in flight per wave): 8 x 2, 12 x 2, 12 x 1, 16 x 2, 16 x 1
             const bool d1 = p.tile_depth == 1;
             if (p.tile_waves == 16)
@@ -3590,56 +3590,51 @@ void launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
                 d1 ? launch_tile<FN, CH, V, G, 12, 1>(p, st, blocks) : launch_tile<FN, CH, V, G, 12>(p, st, blocks);
             else
                 launch_tile<FN, CH, V, G, 8>(p, st, blocks);
+            return true;
         }
+        return false;
     }
-    else if (kind == KIND_SCORE_SHARD_XCD)
-        hipLaunchKernelGGL((score_sharded_xcd_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    else if (kind == KIND_SHARD_BUCKET)
-        hipLaunchKernelGGL((shard_bucket_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    else if (kind == KIND_STEP_FWD_GRAD) {
-        if constexpr (FN != KGE_PROTATE && G <= kFwdGradMaxG) {
+    KGE_KIND(KIND_SCORE_SHARD_XCD, score_sharded_xcd_kernel, FN, CH, V, G)
+    KGE_KIND(KIND_SHARD_BUCKET, shard_bucket_kernel, FN, CH, V, G)
+    if (kind == KIND_STEP_FWD_GRAD) {
+        if constexpr (kind_has(KIND_STEP_FWD_GRAD, FN, CH, G)) {
             if (!p.adversarial)
-                hipLaunchKernelGGL((step_fwd_grad_kernel<FN, CH, V, G, 0>), dim3(blocks), dim3(kBlock), 0, st, p);
+                KGE_LAUNCH(step_fwd_grad_kernel, FN, CH, V, G, 0);
             else if (p.detach)
-                hipLaunchKernelGGL((step_fwd_grad_kernel<FN, CH, V, G, 1>), dim3(blocks), dim3(kBlock), 0, st, p);
+                KGE_LAUNCH(step_fwd_grad_kernel, FN, CH, V, G, 1);
             else
-                hipLaunchKernelGGL((step_fwd_grad_kernel<FN, CH, V, G, 2>), dim3(blocks), dim3(kBlock), 0, st, p);
+                KGE_LAUNCH(step_fwd_grad_kernel, FN, CH, V, G, 2);
+            return true;
         }
+        return false;
     }
-    else if (kind == KIND_STEP_EPILOGUE) {
-        if constexpr (FN != KGE_PROTATE && G <= kFwdGradMaxG)
-            hipLaunchKernelGGL((step_epilogue_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    }
-    else if (kind == KIND_STEP_FWD_STATS) {
-        if constexpr (FN == KGE_INTERHT)
-            hipLaunchKernelGGL((step_fwd_kernel<FN, CH, V, G, true>), dim3(blocks), dim3(kBlock), 0, st, p);
-    }
-    else if (kind == KIND_FINISH) {
-        if constexpr (!CH) hipLaunchKernelGGL((finish_kernel<FN, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-    } else
-        hipLaunchKernelGGL((score_fwd_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
+    KGE_KIND(KIND_STEP_EPILOGUE, step_epilogue_kernel, FN, CH, V, G)
+    KGE_KIND(KIND_STEP_FWD_STATS, step_fwd_kernel, FN, CH, V, G, true)
+    KGE_KIND(KIND_FINISH, finish_kernel, FN, V, G)
+    KGE_KIND(KIND_FWD, score_fwd_kernel, FN, CH, V, G)
+    return false;
 }
+#undef KGE_KIND
 
 template <int FN, bool CH, int V>
 int launch_g(const ScoreParams& p, int kind, hipStream_t st, int blocks, int G) {
+    bool launched = false;
     switch (G) {
-        case 1: launch_one<FN, CH, V, 1>(p, kind, st, blocks); return 0;
-        case 2: launch_one<FN, CH, V, 2>(p, kind, st, blocks); return 0;
-        case 4: launch_one<FN, CH, V, 4>(p, kind, st, blocks); return 0;
-        case 8: launch_one<FN, CH, V, 8>(p, kind, st, blocks); return 0;
+        case 1: launched = launch_one<FN, CH, V, 1>(p, kind, st, blocks); break;
+        case 2: launched = launch_one<FN, CH, V, 2>(p, kind, st, blocks); break;
+        case 4: launched = launch_one<FN, CH, V, 4>(p, kind, st, blocks); break;
+        case 8: launched = launch_one<FN, CH, V, 8>(p, kind, st, blocks); break;
         case 16:
             // dword-per-lane backward for D <= 1024 (kBwdMaxG): every atomic wave-instruction then
             // covers 256 contiguous bytes, the full-rate shape for global float atomics
             if constexpr (V == 1) {
-                if (kind == KIND_BWD) {
-                    hipLaunchKernelGGL((score_bwd_kernel<FN, CH, 1, 16>), dim3(blocks), dim3(kBlock), 0, st, p);
-                    return 0;
-                }
+                if (kind == KIND_BWD) { KGE_LAUNCH(score_bwd_kernel, FN, CH, 1, 16); launched = true; }
             }
-            return KGE_ENOTSUP;
-        default: return KGE_ENOTSUP;
+            break;
     }
+    return launched ? 0 : KGE_ENOTSUP;
 }
+#undef KGE_LAUNCH
 
 template <int FN, bool CH>
 int launch_v(const ScoreParams& p, int kind, hipStream_t st, int blocks, int V, int G) {

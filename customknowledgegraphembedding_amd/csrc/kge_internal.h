@@ -37,7 +37,65 @@ enum Kind {
     KIND_STEP_FWD_TILE = 19,   // kge_step_forward's negatives + positives: row-group x XCD-slice tiles, one
                                // entity-sorted sweep per block (queries in LDS)
     KIND_SCORE_TILE = 20,      // kge_score_indexed in the same order (no positives)
+    KIND_COUNT
 };
+constexpr int kFwdGradMaxG = 4;  // the fused forward + query gradient keeps 6 accumulators per element
+
+// How run_score sizes a kind's grid (kWavesPerBlock waves per counted block; B = p.B, E = p.c_rows)
+enum GridRule {
+    GRID_WAVE_PER_ROW,        // B waves
+    GRID_BLOCK_PER_ROW,       // B blocks
+    GRID_WAVE_PER_ENT,        // E waves
+    GRID_BLOCK_PER_ENT,       // E blocks
+    GRID_XCD_SLICES,          // 8 slice blocks per 4 batch rows (times p.xcd_phases for KIND_STEP_FWD_XCD)
+    GRID_TILE_GROUPS,         // 8 slice blocks per group of p.tile_rows rows, then the next plan's tail blocks
+    GRID_CAND_PER_WAVE,       // B * ceil(N / cpw) waves, cpw picked from the shape
+    GRID_STEP_EPILOGUE,       // a wave per slot (3 B), the event-scatter blocks, one loss block
+    GRID_SHARD_EPILOGUE,      // a wave per slot (2 B), one loss block
+};
+
+// What a kind needs, stated once: run_score checks a launch against its entry and launch_one / launch_shard
+// take their `if constexpr` guards from the same entry (kind_has), so the host check and the set of
+// instantiations cannot disagree. A new kind is one enum entry, one row here, one case of run_score's grid
+// switch if its grid shape is new, and one branch of launch_one.
+struct KindInfo {
+    GridRule grid;
+    bool ch;            // head-batch selects the CH instantiation (false: the kernel has the tail formula only)
+    int max_g;          // groups per lane the kernel is instantiated for
+    bool g_whole_waves; // G % kWavesPerBlock == 0: every wave of the block owns whole column groups
+    bool no_protate;    // the fused forward + query gradient family: no pRotatE modulus gradient
+    bool interht_only;  // keeps InterHT's candidate norms
+    const char* what;   // check_launch's name for the launch
+};
+constexpr KindInfo kKinds[KIND_COUNT] = {
+    /* KIND_FWD */             {GRID_CAND_PER_WAVE, true, kMaxG, false, false, false, "kge score launch"},
+    /* KIND_BWD */             {GRID_CAND_PER_WAVE, true, kBwdMaxG, false, false, false, "kge score backward launch"},
+    /* KIND_FINISH */          {GRID_WAVE_PER_ROW, false, kMaxG, false, false, false, "kge finish launch"},
+    /* KIND_BWD_ROWS */        {GRID_BLOCK_PER_ROW, true, kMaxG, false, false, false, "kge score launch"},
+    /* KIND_BWD_ENT */         {GRID_WAVE_PER_ENT, true, kMaxG, false, false, false, "kge score launch"},
+    /* KIND_BWD_STREAM */      {GRID_BLOCK_PER_ROW, true, kMaxG, true, false, false, "kge score launch"},
+    /* KIND_BWD_CHAIN */       {GRID_WAVE_PER_ROW, true, kMaxG, false, false, false, "kge score launch"},
+    /* KIND_FWD_STATS */       {GRID_CAND_PER_WAVE, true, kMaxG, false, false, true, "kge score launch"},
+    /* KIND_STEP_FWD */        {GRID_BLOCK_PER_ROW, true, kMaxG, false, false, false, "kge score launch"},
+    /* KIND_STEP_FWD_STATS */  {GRID_BLOCK_PER_ROW, true, kMaxG, false, false, true, "kge score launch"},
+    /* KIND_BWD_ENT_STREAM */  {GRID_BLOCK_PER_ENT, true, kMaxG, true, false, false, "kge score launch"},
+    /* KIND_STEP_FWD_GRAD */   {GRID_BLOCK_PER_ROW, true, kFwdGradMaxG, false, true, false, "kge score launch"},
+    /* KIND_STEP_EPILOGUE */   {GRID_STEP_EPILOGUE, true, kFwdGradMaxG, false, true, false, "kge score launch"},
+    /* KIND_SHARD_FWD_GRAD */  {GRID_BLOCK_PER_ROW, true, kFwdGradMaxG, false, true, false, "kge score launch"},
+    /* KIND_SHARD_POS */       {GRID_WAVE_PER_ROW, false, kFwdGradMaxG, false, true, false, "kge score launch"},
+    /* KIND_SHARD_EPILOGUE */  {GRID_SHARD_EPILOGUE, true, kFwdGradMaxG, false, true, false, "kge score launch"},
+    /* KIND_STEP_FWD_XCD */    {GRID_XCD_SLICES, true, kMaxG, false, false, false, "kge score launch"},
+    /* KIND_SCORE_SHARD_XCD */ {GRID_XCD_SLICES, true, kMaxG, false, false, false, "kge score launch"},
+    /* KIND_SHARD_BUCKET */    {GRID_XCD_SLICES, true, kMaxG, false, false, false, "kge score launch"},
+    /* KIND_STEP_FWD_TILE */   {GRID_TILE_GROUPS, true, kFwdGradMaxG, false, false, false, "kge score launch"},
+    /* KIND_SCORE_TILE */      {GRID_TILE_GROUPS, true, kFwdGradMaxG, false, false, false, "kge score launch"},
+};
+// whether kind k has a (FN, CH, G) instantiation
+constexpr bool kind_has(int k, int fn, bool ch, int G) {
+    return G <= kKinds[k].max_g && (!kKinds[k].g_whole_waves || G % kWavesPerBlock == 0) &&
+           (!kKinds[k].no_protate || fn != KGE_PROTATE) && (!kKinds[k].interht_only || fn == KGE_INTERHT) &&
+           (kKinds[k].ch || !ch);
+}
 constexpr int kTileBuckets = 256;  // entity buckets of a slice (the block's counting sort)
 constexpr int kTileMaxRows = 16;
 constexpr int kTileLdsMax = 160 * 1024;
@@ -49,7 +107,6 @@ constexpr int tile_nq(int fn) { return (fn == KGE_COMPLEX || fn == KGE_ROTATE ||
 constexpr int shard_nq(int fn) {
     return fn == KGE_INTERHT ? 3 : ((fn == KGE_COMPLEX || fn == KGE_ROTATE) ? 2 : 1);
 }
-constexpr int kFwdGradMaxG = 4;  // the fused forward + query gradient keeps 6 accumulators per element
 
 // ---------------------------------------------------------------------------------------------
 // The planned tile sweep's progress board (kge_step_planner_set_board): one 128-B line per entity slice, one

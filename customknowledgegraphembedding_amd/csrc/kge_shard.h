@@ -426,22 +426,31 @@ __global__ __launch_bounds__(kBlock) void shard_epilogue_kernel(ScoreParams p) {
     }
 }
 
+// Launches shard kind `kind`; false when it has no (FN, CH, V, G) instantiation (nothing was launched).
 template <int FN, bool CH, int V, int G>
-void launch_shard(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
-    if constexpr (FN != KGE_PROTATE && G <= kFwdGradMaxG) {
-        if (kind == KIND_SHARD_FWD_GRAD) {
+bool launch_shard(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
+    if (kind == KIND_SHARD_FWD_GRAD) {
+        if constexpr (kind_has(KIND_SHARD_FWD_GRAD, FN, CH, G)) {
             if (!p.adversarial)
                 hipLaunchKernelGGL((shard_fwd_grad_kernel<FN, CH, V, G, 0>), dim3(blocks), dim3(kBlock), 0, st, p);
             else if (p.detach)
                 hipLaunchKernelGGL((shard_fwd_grad_kernel<FN, CH, V, G, 1>), dim3(blocks), dim3(kBlock), 0, st, p);
             else
                 hipLaunchKernelGGL((shard_fwd_grad_kernel<FN, CH, V, G, 2>), dim3(blocks), dim3(kBlock), 0, st, p);
-        } else if (kind == KIND_SHARD_POS) {
-            if constexpr (!CH) hipLaunchKernelGGL((shard_pos_kernel<FN, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
-        } else if (kind == KIND_SHARD_EPILOGUE) {
+            return true;
+        }
+    } else if (kind == KIND_SHARD_POS) {
+        if constexpr (kind_has(KIND_SHARD_POS, FN, CH, G)) {
+            hipLaunchKernelGGL((shard_pos_kernel<FN, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
+            return true;
+        }
+    } else if (kind == KIND_SHARD_EPILOGUE) {
+        if constexpr (kind_has(KIND_SHARD_EPILOGUE, FN, CH, G)) {
             hipLaunchKernelGGL((shard_epilogue_kernel<FN, CH, V, G>), dim3(blocks), dim3(kBlock), 0, st, p);
+            return true;
         }
     }
+    return false;
 }
 
 }  // namespace kge_impl

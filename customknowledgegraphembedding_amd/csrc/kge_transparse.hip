@@ -257,8 +257,8 @@ ts_rows_kernel(TsParams p) {
             if (p.nrel <= kTsSortMaxRel && p.B <= kTsSortMaxB) {
                 // Relation-sorted order: blocks i and i + 8 share an XCD, each XCD takes a contiguous run of ranks,
                 // and rank k is the k-th batch row in (relation, row) order, so an XCD works through one or two
-                // relations at a time and their M_r tiles (1 MB at d = 500) stay in its L2 (scripts/ts_rel_probe.py:
-                // rows sorted by relation run 0.88x the time of random relations). Outputs go to (b, n) as before.
+                // relations at a time and their M_r tiles (1 MB at d = 500) stay in its L2 (a round-5 probe
+                // whose record was not kept: rows sorted by relation 0.88x the time of random ones). Outputs: (b, n).
                 const int64_t nblk = p.B * p.nchunk, q8 = nblk / 8, r8 = nblk % 8, x = blk % 8;
                 const int64_t rank = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + blk / 8;
                 ch = (int)(rank % p.nchunk);
