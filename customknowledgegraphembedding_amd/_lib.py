@@ -167,6 +167,9 @@ SIGNATURES = {
                                        _c_p, _c_p, ctypes.c_size_t, _c_p, _c_p]),
     "kge_eval_rank_planes_phases": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p,
                                            _c_i64, _c_p, _c_p, ctypes.c_size_t, _c_i, _c_p, _c_p]),
+    "kge_eval_rank_sweep_workspace_size": (_c_i64, [_c_i64, _c_i64]),
+    "kge_eval_rank_sweep": (_c_i, [_c_i, _c_i, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_i64,
+                                   _c_f, _c_f, _c_f, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "kge_gemm_nt_bf16x3_planes_ex": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p,
                                             _c_p]),
     "kge_rank_filtered": (_c_i, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),

@@ -536,6 +536,12 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
             // one wave per slot (negative rows, then positives), then one block for the loss
             waves = (2 * p.B + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock + kWavesPerBlock;
             break;
+        case GRID_RANK_PAIRS: waves = p.B + p.rk.nf; break;
+        case GRID_RANK_SWEEP:
+            // run_score's block count is waves / kWavesPerBlock (the blocks themselves have kSweepWaves waves)
+            if (p.tile_rows < 1 || p.rk.chunks < 1 || p.tile_lds > kTileLdsMax) return fail(KGE_EINVAL, "sweep plan missing");
+            waves = (p.B + p.tile_rows - 1) / p.tile_rows * 8 * p.rk.chunks * kWavesPerBlock;
+            break;
     }
     const int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > INT32_MAX) return fail(KGE_EINVAL, "problem too large for one launch");
@@ -1447,6 +1453,64 @@ int kge_eval_rank_planes_phases(const void* A_planes, int64_t a_rows, const void
     launch_eval_rank_planes(A_planes, a_rows, B_planes, b_rows, K, (int)M, (int)N, truth, filter_ptr, filter_ids,
                             nfilter, ranks, workspace, (hipStream_t)stream, form, phases);
     return check_launch("kge_eval_rank_planes");
+}
+
+int64_t kge_eval_rank_sweep_workspace_size(int64_t B, int64_t nfilter) {
+    if (B < 0 || nfilter < 0) return 0;
+    return eval_rank_ws_bytes(B, nfilter);
+}
+
+int kge_eval_rank_sweep(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
+                        int64_t nrelation, int64_t rel_ld, int64_t rel_off, const int64_t* pos, int64_t B, int64_t D,
+                        float gamma, float emb_range, float modulus, const int64_t* truth, const int64_t* filter_ptr,
+                        const int64_t* filter_ids, int64_t nfilter, int64_t* ranks, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    if (!valid_fn(fn)) return fail(KGE_EINVAL, "unknown score function id " + std::to_string(fn));
+    if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH)
+        return fail(KGE_EINVAL, "kge_eval_rank_sweep: mode must be 0 (head-batch) or 1 (tail-batch)");
+    if (B < 0 || D <= 0 || nentity <= 0 || nrelation <= 0 || nfilter < 0) return fail(KGE_EINVAL, "bad shape");
+    if (fn == KGE_DISTMULT || fn == KGE_COMPLEX)
+        return fail(KGE_ENOTSUP, "kge_eval_rank_sweep: DistMult / ComplEx rank through kge_eval_rank_planes");
+    if (B == 0) return ok();
+    if (!ent || !rel || !pos || !truth || !ranks || !workspace || (nfilter > 0 && (!filter_ptr || !filter_ids)))
+        return fail(KGE_EINVAL, "null pointer");
+    if (B > INT32_MAX || nentity > INT32_MAX || B + nfilter > INT32_MAX || !aligned(workspace, 16))
+        return fail(KGE_EINVAL, "kge_eval_rank_sweep: int32 shapes and a 16-B aligned workspace");
+    if ((int64_t)workspace_bytes < eval_rank_ws_bytes(B, nfilter))
+        return fail(KGE_EINVAL, "kge_eval_rank_sweep: workspace too small");
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
+    ScoreParams p;
+    fill_indexed(p, t, {mode, pos, nullptr, 0, B, nentity});
+    int V = 1, G = 1;
+    int rc = pick_vg(p, V, G);
+    if (rc) return rc;
+    if (G > kSweepMaxG) return fail(KGE_ENOTSUP, "kge_eval_rank_sweep: per-half dim past " + std::to_string(kSweepMaxG * kWave * V));
+    if (nfilter == 0) filter_ptr = filter_ids = nullptr;
+    float* ts = static_cast<float*>(workspace);
+    p.rk.truth = truth;
+    p.rk.fptr = filter_ptr;
+    p.rk.fids = filter_ids;
+    p.rk.nf = nfilter;
+    p.rk.ts = ts;
+    p.rk.cnt = reinterpret_cast<int*>(ts + B);
+    p.rk.fs = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + ((B * 8 + 15) / 16 * 16));
+    // query rows per block: as many operand images as the LDS budget holds, at most kSweepMaxRows
+    const int64_t row_lds = (int64_t)shard_nq(fn) * G * kWave * V * 4 + 8;  // + truth score, count
+    const int64_t R = std::min<int64_t>(std::min<int64_t>(kSweepMaxRows, B), kSweepLdsMax / row_lds);
+    const int64_t groups = (B + R - 1) / R, S = (nentity + 7) / 8;
+    // a grid of fewer than kSweepMinBlocks blocks cuts every slice into contiguous chunks (of at least
+    // 2 kSweepWaves rows: one pair of rows per wave)
+    const int64_t want = (kSweepMinBlocks + groups * 8 - 1) / (groups * 8);
+    const int64_t most = std::max<int64_t>(1, S / (2 * kSweepWaves));
+    p.tile_rows = (int)R;
+    p.tile_lds = (int)(R * row_lds);
+    p.rk.chunks = (int)std::max<int64_t>(1, std::min(want, most));
+    rc = run_score(fn, mode, p, KIND_RANK_PAIRS, stream);
+    if (rc) return rc;
+    rc = run_score(fn, mode, p, KIND_RANK_SWEEP, stream);
+    if (rc) return rc;
+    launch_rank_finish(B, nentity, truth, filter_ptr, filter_ids, workspace, ranks, (hipStream_t)stream);
+    return check_launch("kge_eval_rank_sweep");
 }
 
 int kge_score_dense(int fn, int mode, const float* head, int64_t head_ld, const float* rel, int64_t rel_ld,

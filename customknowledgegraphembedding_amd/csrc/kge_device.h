@@ -371,13 +371,11 @@ struct LdsQuery {
     LdsOperand<V> q0, q1, q2;
 };
 
-template <int FN, bool CH, int V, int G, class Q>
-__device__ __forceinline__ float cand_score(const Cand<FN, V, G>& c, const Q& q, const ScoreParams& p,
-                                            float2* stats = nullptr, vecf<V>* nsg = nullptr) {
-    float acc = 0.f;
+// InterHT's candidate inverse half-norms (1/||a||, 1/||b||; no epsilon, Q7): the part of a candidate's score that
+// does not depend on the query.
+template <int FN, int V, int G>
+__device__ __forceinline__ float2 cand_inv_norms(const Cand<FN, V, G>& c) {
     if constexpr (FN == KGE_INTERHT && V % 2 == 0) {
-        // on packed fp32 pairs (v_pk_fma_f32 / v_pk_mul_f32: two elements per instruction): the fused
-        // train forward is VALU-bound and this is most of its per-candidate work
         typedef float f2 __attribute__((ext_vector_type(2)));
         f2 sa2 = {0.f, 0.f}, sb2 = {0.f, 0.f};
 #pragma unroll
@@ -389,14 +387,90 @@ __device__ __forceinline__ float cand_score(const Cand<FN, V, G>& c, const Q& q,
                 sb2 = bb * bb + sb2;
             }
         const float ia = rsqrt_f(wave_sum(sa2.x + sa2.y)), ib = rsqrt_f(wave_sum(sb2.x + sb2.y));
-        if (stats) *stats = make_float2(ia, ib);  // kept for the streaming phase-1 backward
+        return make_float2(ia, ib);
+    } else if constexpr (FN == KGE_INTERHT) {
+        float sa = 0.f, sb = 0.f;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                sa += c.ca[k].a[i] * c.ca[k].a[i];
+                sb += c.cb[k].a[i] * c.cb[k].a[i];
+            }
+        const float ia = rsqrt_f(wave_sum(sa)), ib = rsqrt_f(wave_sum(sb));
+        return make_float2(ia, ib);
+    } else {
+        return make_float2(0.f, 0.f);
+    }
+}
+
+// "Prepare candidate": everything of a candidate's score that no query enters, done in place on its registers.
+// InterHT: the halves normalised (a / ||a||, b / ||b|| + u); pRotatE: the phases (x / phase_div); the other
+// functions: nothing. cand_score_with<.., PREP = true> then scores the prepared row against any number of
+// queries (rank_sweep_kernel: one preparation per candidate row, not one per pair). The expressions are
+// cand_score's own, statement by statement, so both orders round identically (-ffp-contract=on fuses inside a
+// statement only).
+template <int FN, int V, int G>
+__device__ __forceinline__ void cand_prepare(Cand<FN, V, G>& c, const ScoreParams& p) {
+    if constexpr (FN == KGE_INTERHT) {
+        const float2 inv = cand_inv_norms<FN, V, G>(c);
+        const float ia = inv.x, ib = inv.y;
+        if constexpr (V % 2 == 0) {
+            typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+#pragma unroll
+                for (int i = 0; i < V; i += 2) {
+                    const f2 ah = f2{c.ca[k].a[i], c.ca[k].a[i + 1]} * ia;
+                    const f2 bh = f2{c.cb[k].a[i], c.cb[k].a[i + 1]} * ib + 1.f;
+                    c.ca[k].a[i] = ah.x;
+                    c.ca[k].a[i + 1] = ah.y;
+                    c.cb[k].a[i] = bh.x;
+                    c.cb[k].a[i + 1] = bh.y;
+                }
+        } else {
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    const float ah = c.ca[k].a[i] * ia;
+                    const float bh = c.cb[k].a[i] * ib + 1.f;
+                    c.ca[k].a[i] = ah;
+                    c.cb[k].a[i] = bh;
+                }
+        }
+    } else if constexpr (FN == KGE_PROTATE) {
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const float pc = c.ca[k].a[i] / p.phase_div;
+                c.ca[k].a[i] = pc;
+            }
+    }
+}
+
+// "Score against a query". PREP = false: c holds the raw row and inv its cand_inv_norms (cand_score); PREP =
+// true: c went through cand_prepare (inv unused).
+template <int FN, bool CH, int V, int G, bool PREP, class Q>
+__device__ __forceinline__ float cand_score_with(const Cand<FN, V, G>& c, float2 inv, const Q& q, const ScoreParams& p,
+                                                 vecf<V>* nsg = nullptr) {
+    float acc = 0.f;
+    if constexpr (FN == KGE_INTERHT && V % 2 == 0) {
+        // on packed fp32 pairs (v_pk_fma_f32 / v_pk_mul_f32: two elements per instruction): the fused
+        // train forward is VALU-bound and this is most of its per-candidate work
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        const float ia = inv.x, ib = inv.y;
 #pragma unroll
         for (int k = 0; k < G; ++k) {
             const vecf<V> q0 = q.q0[k], q1 = q.q1[k], q2 = q.q2[k];
 #pragma unroll
             for (int i = 0; i < V; i += 2) {
-                const f2 ah = f2{c.ca[k].a[i], c.ca[k].a[i + 1]} * ia;        // normalised candidate a-half
-                const f2 bh = f2{c.cb[k].a[i], c.cb[k].a[i + 1]} * ib + 1.f;  // normalised b-half + u
+                f2 ah = f2{c.ca[k].a[i], c.ca[k].a[i + 1]}, bh = f2{c.cb[k].a[i], c.cb[k].a[i + 1]};
+                if constexpr (!PREP) {
+                    ah = ah * ia;        // normalised candidate a-half
+                    bh = bh * ib + 1.f;  // normalised b-half + u
+                }
                 const f2 Q0{q0.a[i], q0.a[i + 1]}, Q1{q1.a[i], q1.a[i + 1]}, Q2{q2.a[i], q2.a[i + 1]};
                 // head: a_head * b_tail - a_tail * b_head + re_mid; tail: the other way round (model.py:222)
                 const f2 x = CH ? (ah * Q1 - Q0 * bh + Q2) : (Q0 * bh - ah * Q1 + Q2);
@@ -409,22 +483,16 @@ __device__ __forceinline__ float cand_score(const Cand<FN, V, G>& c, const Q& q,
             }
         }
     } else if constexpr (FN == KGE_INTERHT) {
-        float sa = 0.f, sb = 0.f;
+        const float ia = inv.x, ib = inv.y;
 #pragma unroll
         for (int k = 0; k < G; ++k)
 #pragma unroll
             for (int i = 0; i < V; ++i) {
-                sa += c.ca[k].a[i] * c.ca[k].a[i];
-                sb += c.cb[k].a[i] * c.cb[k].a[i];
-            }
-        const float ia = rsqrt_f(wave_sum(sa)), ib = rsqrt_f(wave_sum(sb));
-        if (stats) *stats = make_float2(ia, ib);  // kept for the streaming phase-1 backward
-#pragma unroll
-        for (int k = 0; k < G; ++k)
-#pragma unroll
-            for (int i = 0; i < V; ++i) {
-                const float ah = c.ca[k].a[i] * ia;        // normalised candidate a-half
-                const float bh = c.cb[k].a[i] * ib + 1.f;  // normalised candidate b-half + u
+                float ah = c.ca[k].a[i], bh = c.cb[k].a[i];
+                if constexpr (!PREP) {
+                    ah = ah * ia;        // normalised candidate a-half
+                    bh = bh * ib + 1.f;  // normalised candidate b-half + u
+                }
                 float x;
                 if (CH)  // a_head * b_tail - a_tail * b_head + re_mid   (model.py:222)
                     x = ah * q.q1[k].a[i] - q.q0[k].a[i] * bh + q.q2[k].a[i];
@@ -469,7 +537,8 @@ __device__ __forceinline__ float cand_score(const Cand<FN, V, G>& c, const Q& q,
                     const float xr = q.q0[k].a[i] - x, xi = q.q1[k].a[i] - y;
                     acc += __builtin_amdgcn_sqrtf(xr * xr + xi * xi);  // hardware sqrt, as the packed form
                 } else if constexpr (FN == KGE_PROTATE) {
-                    const float pc = x / p.phase_div;
+                    float pc = x;
+                    if constexpr (!PREP) pc = x / p.phase_div;
                     const float z = CH ? (pc + q.q0[k].a[i]) : (q.q0[k].a[i] - pc);
                     acc += fabsf(hw_sin(z));  // the hardware v_sin_f32 on the fraction of z's revolutions
                 }
@@ -479,6 +548,16 @@ __device__ __forceinline__ float cand_score(const Cand<FN, V, G>& c, const Q& q,
     if constexpr (FN == KGE_DISTMULT || FN == KGE_COMPLEX) return acc;
     else if constexpr (FN == KGE_PROTATE) return p.gamma - acc * p.modulus;
     else return p.gamma - acc;
+}
+
+template <int FN, bool CH, int V, int G, class Q>
+__device__ __forceinline__ float cand_score(const Cand<FN, V, G>& c, const Q& q, const ScoreParams& p,
+                                            float2* stats = nullptr, vecf<V>* nsg = nullptr) {
+    const float2 inv = cand_inv_norms<FN, V, G>(c);
+    if constexpr (FN == KGE_INTERHT) {
+        if (stats) *stats = inv;  // kept for the streaming phase-1 backward
+    }
+    return cand_score_with<FN, CH, V, G, false>(c, inv, q, p, nsg);
 }
 
 struct WaveTask {
@@ -3534,6 +3613,129 @@ __global__ __launch_bounds__(kBlock) void bwd_ent_stream_kernel(ScoreParams p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Filtered ranks of the distance models without the [B, E] score matrix (kge_eval_rank_sweep; TransE, RotatE,
+// pRotatE, InterHT). rank = 1 + #{e : s_e > s_truth} - #{filter entries f != truth : s_f > s_truth}, the rank of
+// rank_kernel on score_all's matrix: every score here is cand_score's value on the same operands.
+//   1. rank_pairs_kernel, one wave per pair: the score of (q, truth[q]) (-inf for an out-of-range truth) and of
+//      every filter entry (q, f), q the row whose CSR range holds the entry; the waves of the truths also reset
+//      the rows' counts, so the call needs nothing of the workspace from before it;
+//   2. rank_sweep_kernel: block i takes entity slice x = i % 8 (S = ceil(E / 8) rows; blocks i and i + 8 share an
+//      XCD, so a slice's rows are gathered through one XCD's L2), row group g = (i / 8) % groups of R = p.tile_rows
+//      query rows, and chunk i / (8 groups) of the slice's p.rk.chunks contiguous chunks (row groups vary fastest:
+//      the blocks in flight together sweep the same chunk). The R rows' query operands are built as everywhere
+//      else (build_query_for) and kept as LDS images; wave w takes the chunk's rows w, w + NWV, ... two at a time:
+//      both rows loaded into registers, prepared once (cand_prepare: InterHT's norms, pRotatE's phases), then for
+//      each query row one read of its images serves both candidates, and lane r counts the scores above row r's
+//      truth score (strict >: a NaN on either side never counts). The block's counts are summed in LDS and added
+//      to the rows' counts with one integer atomic per row;
+//   3. rank_finish_kernel (kge_eval.hip) subtracts the filter entries above the truth.
+// No ids are read and nothing is sorted: the candidates are the table's rows in order.
+// ---------------------------------------------------------------------------------------------
+template <int FN, bool CH, int V, int G>
+__global__ __launch_bounds__(kBlock) void rank_pairs_kernel(ScoreParams p) {
+    const int64_t pi = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (pi >= p.B + p.rk.nf) return;  // wave-uniform
+    int64_t b, e, j = 0;
+    if (pi < p.B) {
+        b = pi;
+        e = p.rk.truth[pi];
+        if (lane == 0) p.rk.cnt[pi] = 0;
+    } else {
+        j = pi - p.B;
+        e = p.rk.fids[j];
+        int64_t lo = 0, hi = p.B;  // the row whose filter range holds j: the last b with fptr[b] <= j
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (p.rk.fptr[mid] <= j) lo = mid; else hi = mid;
+        }
+        b = lo;
+    }
+    Query<FN, CH, V, G> q;
+    int64_t qi, ri;
+    bool qok, rok, ok;
+    build_query_for<FN, CH, V, G>(p, b, lane, q, qi, ri, qok, rok);
+    Cand<FN, V, G> c;
+    c.load(cand_row(p, e, ok), ok, p.D, lane);
+    cand_prepare<FN, V, G>(c, p);
+    const float s = cand_score_with<FN, CH, V, G, true>(c, make_float2(0.f, 0.f), q, p);
+    if (lane == 0) {
+        if (pi < p.B)
+            p.rk.ts[pi] = ok ? s : -INFINITY;  // rank_kernel's score of an out-of-range truth
+        else
+            p.rk.fs[j] = s;
+    }
+}
+
+template <int FN, bool CH, int V, int G, int NWV>
+__global__ __launch_bounds__(NWV * kWave) void rank_sweep_kernel(ScoreParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sweep_smem[];
+    constexpr int NQ = shard_nq(FN);  // operand images per query row
+    constexpr int W = G * kWave;
+    static_assert(kSweepMaxRows <= kWave, "one lane per query row");
+    const int R = p.tile_rows;
+    vecf<V>* qimg = reinterpret_cast<vecf<V>*>(sweep_smem);  // [R][NQ][W]
+    float* tsl = reinterpret_cast<float*>(qimg + (size_t)R * NQ * W);  // [R] truth scores
+    int* cl = reinterpret_cast<int*>(tsl + R);                          // [R] the block's counts
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int x = (int)(blockIdx.x & 7);
+    const int64_t groups = (p.B + R - 1) / R, rest = blockIdx.x >> 3;
+    const int64_t ck = rest / groups, g0 = (rest - ck * groups) * R;
+    const int nr = (int)min<int64_t>(R, p.B - g0);
+    const int64_t S = (p.c_rows + 7) / 8;
+    const int64_t e_lo = min((int64_t)x * S, p.c_rows), e_hi = min(p.c_rows, e_lo + S);
+    const int64_t CS = (S + p.rk.chunks - 1) / p.rk.chunks;
+    const int64_t lo = min(e_lo + ck * CS, e_hi), hi = min(e_hi, lo + CS);
+    if (nr <= 0 || lo >= hi) return;  // block-uniform (an empty slice or chunk)
+
+    for (int r = w; r < nr; r += NWV) {
+        Query<FN, CH, V, G> q;
+        int64_t qi, ri;
+        bool qok, rok;
+        build_query_for<FN, CH, V, G>(p, g0 + r, lane, q, qi, ri, qok, rok);
+        vecf<V>* qr = qimg + (size_t)r * NQ * W;
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            qr[lane + k * kWave] = q.q0[k];
+            if constexpr (NQ > 1) qr[W + lane + k * kWave] = q.q1[k];
+            if constexpr (NQ > 2) qr[2 * W + lane + k * kWave] = q.q2[k];
+        }
+    }
+    if (t < nr) {
+        tsl[t] = p.rk.ts[g0 + t];
+        cl[t] = 0;
+    }
+    __syncthreads();
+    const float my_ts = tsl[lane < nr ? lane : 0];  // lane r: row r's truth score
+    int my_cnt = 0;                                 // lane r: row r's count
+    for (int64_t e = lo + w; e < hi; e += 2 * NWV) {
+        const int64_t e1 = e + NWV;
+        const bool has1 = e1 < hi;  // wave-uniform
+        Cand<FN, V, G> c0, c1;
+        c0.load(p.cent + e * p.c_ld, true, p.D, lane);
+        c1.load(p.cent + (has1 ? e1 : e) * p.c_ld, has1, p.D, lane);
+        cand_prepare<FN, V, G>(c0, p);
+        cand_prepare<FN, V, G>(c1, p);
+        for (int r = 0; r < nr; ++r) {
+            const vecf<V>* qr = qimg + (size_t)r * NQ * W;
+            Query<FN, CH, V, G> q;  // one read of the row's images for both candidates
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                q.q0[k] = qr[lane + k * kWave];
+                if constexpr (NQ > 1) q.q1[k] = qr[W + lane + k * kWave];
+                if constexpr (NQ > 2) q.q2[k] = qr[2 * W + lane + k * kWave];
+            }
+            const float s0 = cand_score_with<FN, CH, V, G, true>(c0, make_float2(0.f, 0.f), q, p);
+            const float s1 = cand_score_with<FN, CH, V, G, true>(c1, make_float2(0.f, 0.f), q, p);
+            if (lane == r) my_cnt += (s0 > my_ts ? 1 : 0) + ((has1 && s1 > my_ts) ? 1 : 0);
+        }
+    }
+    if (lane < nr && my_cnt) atomicAdd(&cl[lane], my_cnt);
+    __syncthreads();
+    if (t < nr && cl[t]) atomicAdd(&p.rk.cnt[g0 + t], cl[t]);
+}
+
 }  // namespace kge_impl
 
 #include "kge_shard.h"
@@ -3590,6 +3792,19 @@ bool launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
                 d1 ? launch_tile<FN, CH, V, G, 12, 1>(p, st, blocks) : launch_tile<FN, CH, V, G, 12>(p, st, blocks);
             else
                 launch_tile<FN, CH, V, G, 8>(p, st, blocks);
+            return true;
+        }
+        return false;
+    }
+    KGE_KIND(KIND_RANK_PAIRS, rank_pairs_kernel, FN, CH, V, G)
+    if (kind == KIND_RANK_SWEEP) {
+        if constexpr (kind_has(KIND_RANK_SWEEP, FN, CH, G)) {
+            static const bool lds_ok =
+                hipFuncSetAttribute(reinterpret_cast<const void*>(rank_sweep_kernel<FN, CH, V, G, kSweepWaves>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, kTileLdsMax) == hipSuccess;
+            (void)lds_ok;
+            hipLaunchKernelGGL((rank_sweep_kernel<FN, CH, V, G, kSweepWaves>), dim3(blocks), dim3(kSweepWaves * kWave),
+                               p.tile_lds, st, p);
             return true;
         }
         return false;

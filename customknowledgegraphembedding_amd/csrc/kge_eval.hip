@@ -1308,6 +1308,16 @@ int launch_eval_rank_planes(const void* Ap, int64_t a_rows, const void* Bp, int6
     return 0;
 }
 
+int launch_rank_finish(int64_t M, int64_t N, const int64_t* truth, const int64_t* fptr, const int64_t* fids, void* ws,
+                       int64_t* ranks, hipStream_t st) {
+    const float* ts = static_cast<const float*>(ws);
+    const int* gcnt = reinterpret_cast<const int*>(ts + M);
+    const float* fs = reinterpret_cast<const float*>(static_cast<const unsigned char*>(ws) + ((M * 8 + 15) / 16 * 16));
+    hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)((M + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0,
+                       st, M, N, truth, fptr, fids, ts, fs, gcnt, ranks);
+    return 0;
+}
+
 int launch_rank(const float* S, int64_t M, int64_t N, int64_t ld, const int64_t* truth, const int64_t* fptr,
                 const int64_t* fids, int64_t* ranks, hipStream_t st) {
     hipLaunchKernelGGL(rank_kernel, dim3((unsigned)M), dim3(kBlock), 0, st, S, M, N, ld, truth, fptr, fids, ranks);

@@ -37,9 +37,19 @@ enum Kind {
     KIND_STEP_FWD_TILE = 19,   // kge_step_forward's negatives + positives: row-group x XCD-slice tiles, one
                                // entity-sorted sweep per block (queries in LDS)
     KIND_SCORE_TILE = 20,      // kge_score_indexed in the same order (no positives)
+    KIND_RANK_PAIRS = 21,      // kge_eval_rank_sweep: the truths' and the filter entries' scores (one wave per pair)
+    KIND_RANK_SWEEP = 22,      // kge_eval_rank_sweep: every entity row against a group of query rows, counting
     KIND_COUNT
 };
 constexpr int kFwdGradMaxG = 4;  // the fused forward + query gradient keeps 6 accumulators per element
+// rank_sweep_kernel: a wave holds two candidate rows and one query's operands in registers (G = 8 would spill)
+constexpr int kSweepMaxG = 4;
+// waves per block: 4 per SIMD (every G <= 4 instance stays under 128 VGPRs), so one wave's LDS query reads overlap
+// another's VALU work; 8 waves measured 3-5 % slower, InterHT d 1 000 15 % (profiles/r08_rank_sweep_ab.txt)
+constexpr int kSweepWaves = 16;
+constexpr int kSweepMaxRows = 16;         // query rows per block
+constexpr int kSweepLdsMax = 144 * 1024;  // operand images of one block
+constexpr int kSweepMinBlocks = 256;      // blocks wanted before an entity slice is cut into chunks (one per CU)
 
 // How run_score sizes a kind's grid (kWavesPerBlock waves per counted block; B = p.B, E = p.c_rows)
 enum GridRule {
@@ -52,6 +62,8 @@ enum GridRule {
     GRID_CAND_PER_WAVE,       // B * ceil(N / cpw) waves, cpw picked from the shape
     GRID_STEP_EPILOGUE,       // a wave per slot (3 B), the event-scatter blocks, one loss block
     GRID_SHARD_EPILOGUE,      // a wave per slot (2 B), one loss block
+    GRID_RANK_PAIRS,          // a wave per pair: B truths, then p.rk.nf filter entries
+    GRID_RANK_SWEEP,          // a block per (group of p.tile_rows rows, entity slice, chunk of p.rk.chunks)
 };
 
 // What a kind needs, stated once: run_score checks a launch against its entry and launch_one / launch_shard
@@ -66,6 +78,7 @@ struct KindInfo {
     bool no_protate;    // the fused forward + query gradient family: no pRotatE modulus gradient
     bool interht_only;  // keeps InterHT's candidate norms
     const char* what;   // check_launch's name for the launch
+    bool distance_only = false;  // TransE, RotatE, pRotatE, InterHT (DistMult / ComplEx rank through the planes)
 };
 constexpr KindInfo kKinds[KIND_COUNT] = {
     /* KIND_FWD */             {GRID_CAND_PER_WAVE, true, kMaxG, false, false, false, "kge score launch"},
@@ -89,10 +102,13 @@ constexpr KindInfo kKinds[KIND_COUNT] = {
     /* KIND_SHARD_BUCKET */    {GRID_XCD_SLICES, true, kMaxG, false, false, false, "kge score launch"},
     /* KIND_STEP_FWD_TILE */   {GRID_TILE_GROUPS, true, kFwdGradMaxG, false, false, false, "kge score launch"},
     /* KIND_SCORE_TILE */      {GRID_TILE_GROUPS, true, kFwdGradMaxG, false, false, false, "kge score launch"},
+    /* KIND_RANK_PAIRS */      {GRID_RANK_PAIRS, true, kSweepMaxG, false, false, false, "kge_eval_rank_sweep", true},
+    /* KIND_RANK_SWEEP */      {GRID_RANK_SWEEP, true, kSweepMaxG, false, false, false, "kge_eval_rank_sweep", true},
 };
 // whether kind k has a (FN, CH, G) instantiation
 constexpr bool kind_has(int k, int fn, bool ch, int G) {
     return G <= kKinds[k].max_g && (!kKinds[k].g_whole_waves || G % kWavesPerBlock == 0) &&
+           (!kKinds[k].distance_only || (fn != KGE_DISTMULT && fn != KGE_COMPLEX)) &&
            (!kKinds[k].no_protate || fn != KGE_PROTATE) && (!kKinds[k].interht_only || fn == KGE_INTERHT) &&
            (kKinds[k].ch || !ch);
 }
@@ -205,6 +221,18 @@ struct ScoreParams {
     const int* tile_plan; // step_fwd_tile_kernel: this batch's plan (kge_step_forward_planned), or null
     int tile_blocks;      // step_fwd_tile_kernel: scoring blocks; blocks past them make the next batch's plan
     PlanArgs tile_next;   // ... that plan (tile_next.plan null: none)
+    // kge_eval_rank_sweep (rank_pairs_kernel, rank_sweep_kernel; tile_rows / tile_lds: the sweep's rows per block
+    // and dynamic LDS bytes)
+    struct {
+        const int64_t* truth;  // [B]
+        const int64_t* fptr;   // [B + 1] filter CSR, or null
+        const int64_t* fids;   // [nf]
+        int64_t nf;
+        float* ts;             // [B] the truths' scores
+        int* cnt;              // [B] entities scoring above the truth
+        float* fs;             // [nf] the filter entries' scores
+        int chunks;            // contiguous chunks an entity slice is cut into (one block per chunk and row group)
+    } rk;
     float* out;
     int64_t out_ld;
     int64_t B, N;
@@ -313,6 +341,9 @@ int64_t eval_rank_ws_bytes(int64_t M, int64_t F);
 int launch_eval_rank_planes(const void* Ap, int64_t a_rows, const void* Bp, int64_t b_rows, int64_t K, int M, int N,
                             const int64_t* truth, const int64_t* fptr, const int64_t* fids, int64_t F, int64_t* ranks,
                             void* ws, hipStream_t st, int form, int phases);
+// rank_finish_kernel alone on a workspace of eval_rank_ws_bytes' layout (kge_eval_rank_sweep)
+int launch_rank_finish(int64_t M, int64_t N, const int64_t* truth, const int64_t* fptr, const int64_t* fids, void* ws,
+                       int64_t* ranks, hipStream_t st);
 int launch_rank(const float* S, int64_t M, int64_t N, int64_t ld, const int64_t* truth, const int64_t* fptr,
                 const int64_t* fids, int64_t* ranks, hipStream_t st);
 

@@ -10,7 +10,10 @@ The scores of a query batch against all E entities are computed on the GPU:
 Ranks are exact integers from kge_rank_filtered: rank = 1 + #(unfiltered e != truth with
 s_e > s_truth). Ties count in the positive's favour; upstream's unstable argsort leaves them
 arbitrary, which no test here exercises (continuous random scores). test_step ranks DistMult / ComplEx batches
-without materialising S (kge_eval_rank_planes: the same ranks).
+without materialising S (kge_eval_rank_planes: the same ranks), and TransE / RotatE / pRotatE / InterHT batches
+through rank_sweep (kge_eval_rank_sweep: each entity row loaded once per group of query rows, prepared once and
+compared with every query's truth score on the spot: the same ranks); score_all + rank_filtered remains the
+path of TranSparse and of widths the sweep has no kernel for.
 """
 from __future__ import annotations
 
@@ -192,6 +195,71 @@ def rank_planes(model, positive_sample: torch.Tensor, mode: str, planes: torch.T
     return ranks
 
 
+SWEEP_FNS = ("TransE", "RotatE", "pRotatE", "InterHT")
+_SWEEP_WS = {}
+_ENOTSUP = -95  # KGE_ENOTSUP (include/kge_hip.h)
+
+
+def _sweep_rank_ok(model) -> bool:
+    """Whether test_step ranks this model through rank_sweep: the distance functions with their tables on a GPU
+    (each measured faster than the score-matrix path by DESIGN §3.0's rule, §3.4). rank_sweep itself may still
+    answer None (a width it has no kernel for): test_step then falls back to score_all + rank_filtered for that
+    batch."""
+    return model.model_name in SWEEP_FNS and model.entity_embedding.device.type == "cuda"
+
+
+def rank_sweep(model, positive_sample: torch.Tensor, mode: str, truth: torch.Tensor,
+               filter_ptr: torch.Tensor | None = None, filter_ids: torch.Tensor | None = None,
+               nfilter: int | None = None) -> torch.Tensor | None:
+    """Filtered ranks of a query batch against every entity for TransE / RotatE / pRotatE / InterHT, without the
+    [B, E] score matrix (kge_eval_rank_sweep: the truth's and the filter entries' scores, a sweep that loads each
+    entity row once per group of query rows and counts the scores above the truth's, the filter correction):
+    rank_filtered(score_all(...))'s ranks exactly. None where the library has no sweep for the model (DistMult /
+    ComplEx / TranSparse, a per-half width past 1 024): callers fall back. filter_ptr must start at 0; nfilter =
+    filter_ptr[-1] (read from the device when not given). The index tensors must be int64, contiguous and on the
+    tables' device (ValueError otherwise)."""
+    if model.model_name not in FN_IDS:
+        return None
+    ent, rel = model.entity_embedding.detach(), model.relation_embedding.detach()
+    dev = ent.device
+    if positive_sample.dim() != 2 or positive_sample.shape[1] != 3:
+        raise ValueError("rank_sweep: positive_sample must be [B, 3]")
+    B, E = positive_sample.shape[0], ent.shape[0]
+    if filter_ptr is None:
+        filter_ids = None
+    for name, t, n in (("positive_sample", positive_sample, 3 * B), ("truth", truth, B),
+                       ("filter_ptr", filter_ptr, B + 1), ("filter_ids", filter_ids, None)):
+        if t is None:
+            continue
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"rank_sweep: {name} must be a contiguous int64 tensor on {dev}")
+        if n is not None and t.numel() != n:
+            raise ValueError(f"rank_sweep: {name} has {t.numel()} elements, expected {n}")
+    ops._need_gpu(ent, rel)
+    lib = _lib.load()
+    nf = (int(filter_ptr[-1]) if nfilter is None else int(nfilter)) if filter_ptr is not None else 0
+    if nf > 0 and (filter_ids is None or filter_ids.numel() < nf):
+        raise ValueError("rank_sweep: filter_ids shorter than nfilter")
+    st = torch.cuda.current_stream(dev).cuda_stream
+    key = (str(dev), st)
+    wsb = int(lib.kge_eval_rank_sweep_workspace_size(B, nf))
+    ws = _SWEEP_WS.get(key)
+    if ws is None or ws.numel() < wsb:
+        ws = _SWEEP_WS[key] = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    ranks = torch.empty(B, dtype=torch.int64, device=dev)
+    modulus = float(model.modulus.detach().reshape(-1)[0]) if model.model_name == "pRotatE" else 0.0
+    rc = lib.kge_eval_rank_sweep(FN_IDS[model.model_name], ops.mode_id(mode), ent.data_ptr(), E, ent.stride(0),
+                                 rel.data_ptr(), rel.shape[0], rel.stride(0), model._rel_off,
+                                 positive_sample.data_ptr(), B, model._D, model._gamma_f, model._range_f, modulus,
+                                 truth.data_ptr(), None if filter_ptr is None else filter_ptr.data_ptr(),
+                                 None if filter_ids is None or nf == 0 else filter_ids.data_ptr(), nf,
+                                 ranks.data_ptr(), ws.data_ptr(), ws.numel(), st)
+    if rc == _ENOTSUP:
+        return None
+    check(rc, "kge_eval_rank_sweep")
+    return ranks
+
+
 class RankPipeline:
     """rank_planes over consecutive query batches on two streams: batch i runs its whole chain (query planes,
     kge_eval_rank_planes_phases' pair scores, counting GEMM and finish) on stream i % 2, with a query-plane buffer and
@@ -369,6 +437,7 @@ def test_step(model, test_triples, all_true_triples, args=None, batch_size=None)
                                                  torch.from_numpy(ids[p[0]:p[-1]]), int(p[-1] - p[0])))
             pipe.flush()
             all_ranks = [r.cpu().numpy() for r in all_ranks]
+        sweep = _sweep_rank_ok(model)
         for mode in (() if all_ranks else ("head-batch", "tail-batch")):
             col = 0 if mode == "head-batch" else 2
             ptr, ids = build_filter(triples, mode, all_true_triples)
@@ -379,7 +448,11 @@ def test_step(model, test_triples, all_true_triples, args=None, batch_size=None)
                 fptr = torch.from_numpy(p - p[0]).to(dev)
                 fids = torch.from_numpy(ids[p[0]:p[-1]]).to(dev)
                 truth = pos[:, col].contiguous()
-                r = rank_filtered(score_all(model, pos, mode, planes=planes), truth, fptr, fids)
+                # the distance functions: ranks from one sweep of the table per group of query rows (no [B, E]
+                # score matrix); the matrix path where the sweep does not apply
+                r = rank_sweep(model, pos, mode, truth, fptr, fids, int(p[-1] - p[0])) if sweep else None
+                if r is None:
+                    r = rank_filtered(score_all(model, pos, mode, planes=planes), truth, fptr, fids)
                 all_ranks.append(r.cpu().numpy())
     ranks = np.concatenate(all_ranks) if all_ranks else np.zeros(0, dtype=np.int64)
     if world > 1:
@@ -389,5 +462,5 @@ def test_step(model, test_triples, all_true_triples, args=None, batch_size=None)
     return metrics_from_ranks(ranks)
 
 
-__all__ = ["build_filter", "score_all", "rank_filtered", "rank_planes", "RankPipeline", "metrics_from_ranks", "test_step", "entity_planes",
+__all__ = ["build_filter", "score_all", "rank_filtered", "rank_planes", "rank_sweep", "RankPipeline", "metrics_from_ranks", "test_step", "entity_planes",
            "split_planes", "HEAD_BATCH", "TAIL_BATCH"]
