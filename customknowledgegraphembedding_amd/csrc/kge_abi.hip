@@ -64,12 +64,13 @@ constexpr int kLossBlock = 1024;
 __global__ __launch_bounds__(kLossBlock) void step_loss_kernel(const float* __restrict__ out_neg,
                                                                const float* __restrict__ out_pos,
                                                                const float* __restrict__ w, int64_t B,
-                                                               float* __restrict__ loss, float* __restrict__ d_out) {
+                                                               float* __restrict__ loss, float* __restrict__ d_out,
+                                                               float* __restrict__ parts) {
     __shared__ float red[3][kLossBlock];
     const int t = threadIdx.x;
     float sw = 0.f, sp = 0.f, sn = 0.f;
     for (int64_t b = t; b < B; b += kLossBlock) {
-        const float wb = w[b];
+        const float wb = w ? w[b] : 1.f;  // no weights (kge_train_step_reg's uni_weight): plain means
         sw += wb;
         sp += wb * out_pos[b];
         sn += wb * out_neg[b];
@@ -88,13 +89,83 @@ __global__ __launch_bounds__(kLossBlock) void step_loss_kernel(const float* __re
     }
     const float tw = red[0][0];
     if (t == 0 && loss) *loss = (-red[1][0] / tw + -red[2][0] / tw) / 2.f;
+    if (t == 0 && parts) {  // positive_sample_loss, negative_sample_loss
+        parts[0] = -red[1][0] / tw;
+        parts[1] = -red[2][0] / tw;
+    }
     if (d_out) {
         const float c = -0.5f / tw;
-        for (int64_t b = t; b < B; b += kLossBlock) d_out[b] = c * w[b];
+        for (int64_t b = t; b < B; b += kLossBlock) d_out[b] = c * (w ? w[b] : 1.f);
     }
 }
 
 __global__ void add_scalar_kernel(const float* __restrict__ x, float* __restrict__ acc) { *acc += *x; }
+
+// ---------------------------------------------------------------------------------------------
+// Value of the L3 ("N3") regulariser of kge_train_step_reg (model.py:4-44; upstream train_step):
+// lambda (sum |entity|^3 + sum |relation|^3) over the tables as they were before the step's update, every
+// sum in a fixed order (no float atomics).
+//   reg_chunk_kernel: blocks [0, nb_ent) each sum kRegChunk of the per-wave partials phase 2 left of the entity
+//     rows it held; the blocks after them each sum |x|^3 over kRegChunk elements of the relation table (the
+//     table's width of every row, never the padding), BEFORE bwd_rel_kernel updates it in place.
+//   reg_finish_kernel: one block sums the chunk sums in index order, adds the term to the loss (and the loss to
+//     the running Sum metric) and writes upstream's log {loss, positive_sample_loss, negative_sample_loss,
+//     regularization}.
+// ---------------------------------------------------------------------------------------------
+constexpr int kRegChunk = 4096;
+__device__ __forceinline__ float block_tree_sum(float s, float* red, int t) {
+    red[t] = s;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(kBlock) void reg_chunk_kernel(const float* __restrict__ part, int64_t nparts,
+                                                           int64_t nb_ent, const float* __restrict__ rel,
+                                                           int64_t rel_ld, int64_t rel_dim, int64_t nrel,
+                                                           float* __restrict__ out) {
+    __shared__ float red[kBlock];
+    const int t = threadIdx.x;
+    float s = 0.f;
+    if ((int64_t)blockIdx.x < nb_ent) {
+        const int64_t lo = (int64_t)blockIdx.x * kRegChunk, hi = min(nparts, lo + kRegChunk);
+        for (int64_t i = lo + t; i < hi; i += kBlock) s += part[i];
+    } else {
+        const int64_t lo = ((int64_t)blockIdx.x - nb_ent) * kRegChunk, hi = min(nrel, lo + kRegChunk);
+        for (int64_t i = lo + t; i < hi; i += kBlock) {
+            const int64_t r = i / rel_dim;
+            const float x = fabsf(rel[r * rel_ld + (i - r * rel_dim)]);
+            s += x * x * x;
+        }
+    }
+    s = block_tree_sum(s, red, t);
+    if (t == 0) out[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kBlock) void reg_finish_kernel(const float* __restrict__ chunk, int64_t nchunks,
+                                                            float lambda, const float* __restrict__ parts,
+                                                            float* __restrict__ loss, float* __restrict__ loss_sum,
+                                                            float* __restrict__ log) {
+    __shared__ float red[kBlock];
+    const int t = threadIdx.x;
+    float s = 0.f;
+    for (int64_t i = t; i < nchunks; i += kBlock) s += chunk[i];
+    s = block_tree_sum(s, red, t);
+    if (t != 0) return;
+    const float reg = nchunks > 0 ? lambda * s : 0.f;
+    const float total = *loss + reg;  // upstream: loss = loss + regularization, before backward() and the log
+    *loss = total;
+    if (loss_sum) *loss_sum += total;
+    if (log) {
+        log[0] = total;
+        log[1] = parts[0];
+        log[2] = parts[1];
+        log[3] = reg;
+    }
+}
 
 __global__ __launch_bounds__(kBlock) void log_sigmoid_bwd_kernel(const float* __restrict__ x,
                                                                  const float* __restrict__ d_out, int64_t n,
@@ -252,6 +323,7 @@ struct RelAdam {
     float *p, *m, *v;
     AdamArgs a;
     int on;
+    float reg3;  // 3 lambda of the L3 regulariser: every column of the table's width gets reg3 x |x| (0: off)
 };
 
 constexpr int kRelWaves = 16;  // waves per relation chunk: each scans 1/16 of the slots (fewer dependent rounds)
@@ -309,6 +381,7 @@ __global__ __launch_bounds__(kRelWaves * kWave) void bwd_rel_kernel(const int64_
     if (ra.on) {
         const int64_t e = rho * rel_ld + c;
         float p = ra.p[e], m = ra.m[e], v = ra.v[e];
+        if (ra.reg3 != 0.f) g += ra.reg3 * (p * fabsf(p));  // the unread parts too: their data gradient is 0
         adam_update(p, g, m, v, ra.a.b1, ra.a.b2, ra.a.eps, ra.a.alpha, ra.a.step_size, ra.a.bc2_sqrt, ra.a.keras);
         ra.p[e] = p;
         ra.m[e] = m;
@@ -1585,7 +1658,7 @@ int kge_step_loss(const float* out_neg, const float* out_pos, const float* weigh
     if (B <= 0) return fail(KGE_EINVAL, "kge_step_loss needs B > 0");
     if (!out_neg || !out_pos || !weight || (!loss && !d_out)) return fail(KGE_EINVAL, "null pointer");
     hipLaunchKernelGGL(step_loss_kernel, dim3(1), dim3(kLossBlock), 0, (hipStream_t)stream, out_neg, out_pos, weight, B,
-                       loss, d_out);
+                       loss, d_out, (float*)nullptr);
     return check_launch("kge_step_loss");
 }
 
@@ -1721,6 +1794,13 @@ struct StepOpts {
     bool fused_dscores = false; // the positive score gradient comes out of the neg_reduce_bwd launch
     bool epilogue_done = false; // score gradients and both slots' chains done (KIND_STEP_EPILOGUE)
     float *rel_p = nullptr, *rel_m = nullptr, *rel_v = nullptr;  // Adam on the relation table, fused
+    // kge_train_step_reg: the L3 regulariser (lambda; needs the fused Adam) and, with reg_finish, the launch that
+    // adds its value to the loss and writes the log, between the entity pass and the relation update
+    float reg = 0.f;
+    bool reg_finish = false;
+    float *reg_part = nullptr, *reg_chunk = nullptr;  // workspace: per-wave partials [4 E], chunk sums
+    const float* loss_parts = nullptr;                // [2] positive and negative sample loss
+    float *loss = nullptr, *loss_sum = nullptr, *log = nullptr;
 };
 
 static EvArgs ev_args(const Batch& b, int64_t E) {
@@ -1881,10 +1961,28 @@ static int step_backward_impl(const Tables& t, const Batch& b, const StepGrads& 
     q.ent_w = ent_w;
     q.d_out_ent = g.d_ent;
     if (adam) set_adam(q, *adam, m_ent, v_ent);
+    const float reg3 = adam ? 3.f * o.reg : 0.f;
+    q.reg3 = reg3;
+    q.reg_part = o.reg_part;
     if (t.nentity > 0) {
         // streaming form (block per row, waves split the columns) under the same condition as phase 1
         rc = run_score(fn, mode, q, stream_form(G1) ? KIND_BWD_ENT_STREAM : KIND_BWD_ENT, stream);
         if (rc) return rc;
+    }
+    if (o.reg_finish) {
+        // the regulariser's value from the entity pass' partials and the relation table, still unchanged
+        int64_t nparts = 0, nb_ent = 0, nb_rel = 0;
+        if (reg3 != 0.f) {
+            nparts = t.nentity * (stream_form(G1) ? kWavesPerBlock : 1);
+            nb_ent = (nparts + kRegChunk - 1) / kRegChunk;
+            nb_rel = (t.nrelation * rel_dim + kRegChunk - 1) / kRegChunk;
+            if (nb_ent + nb_rel > 0)
+                hipLaunchKernelGGL(reg_chunk_kernel, dim3((unsigned)(nb_ent + nb_rel)), dim3(kBlock), 0, st,
+                                   o.reg_part, nparts, nb_ent, t.rel, t.rel_ld, rel_dim, t.nrelation * rel_dim,
+                                   o.reg_chunk);
+        }
+        hipLaunchKernelGGL(reg_finish_kernel, dim3(1), dim3(kBlock), 0, st, o.reg_chunk, nb_ent + nb_rel, o.reg,
+                           o.loss_parts, o.loss, o.loss_sum, o.log);
     }
     // 5. relation rows (slot order) and the pRotatE modulus
     if (t.nrelation > 0 || g.d_modulus) {
@@ -1897,6 +1995,7 @@ static int step_backward_impl(const Tables& t, const Batch& b, const StepGrads& 
             ra.v = o.rel_v;
             ra.a = *adam;
             ra.on = 1;
+            ra.reg3 = reg3;
         }
         hipLaunchKernelGGL(bwd_rel_kernel, dim3((unsigned)rb), dim3(kRelWaves * kWave), 0, st, b.pos, B, t.nrelation,
                            w.qg_rel, rel_w, t.rel_off, g.d_rel, t.rel_ld, rel_dim, w.dmod, g.d_modulus, ra);
@@ -2011,25 +2110,66 @@ int64_t kge_train_step_workspace_size(int fn, int64_t nentity, int64_t nrelation
     return train_ws_layout(nullptr, fn, nentity, nrelation, rel_ld, B, N, D).bytes;
 }
 
-int kge_train_step(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld, float* rel, int64_t nrelation,
-                   int64_t rel_ld, int64_t rel_off, const int64_t* pos, const int64_t* neg, int64_t neg_ld, int64_t B,
-                   int64_t N, int64_t D, float gamma, float emb_range, float temperature, int adversarial, int detach,
-                   const float* weight, float* loss, float* loss_sum, float* out_neg, float* out_pos,
-                   float* m_ent, float* v_ent, float* m_rel, float* v_rel, float lr, float beta1, float beta2,
-                   float eps, int64_t step, int keras, void* workspace, int64_t workspace_bytes, void* stream) {
+// kge_train_step_reg's workspace: kge_train_step's, then the regulariser's per-wave partials (four per entity
+// row), the chunk sums of reg_chunk_kernel and the two loss parts
+struct RegWs {
+    float *part, *chunk, *loss_parts;
+    int64_t bytes;
+};
+
+static RegWs reg_ws_layout(char* base, int64_t train_bytes, int64_t E, int64_t R, int64_t rel_ld) {
+    RegWs r;
+    int64_t o = train_bytes;
+    auto take = [&](int64_t bytes) {
+        char* p = base ? base + o : nullptr;
+        o += align256(bytes);
+        return (float*)p;
+    };
+    const int64_t nparts = E * kWavesPerBlock;
+    r.part = take(nparts * 4);
+    r.chunk = take(((nparts + kRegChunk - 1) / kRegChunk + (R * rel_ld + kRegChunk - 1) / kRegChunk) * 4);
+    r.loss_parts = take(2 * 4);
+    r.bytes = o;
+    return r;
+}
+
+int64_t kge_train_step_reg_workspace_size(int fn, int64_t nentity, int64_t nrelation, int64_t rel_ld, int64_t B,
+                                          int64_t N, int64_t D) {
+    const int64_t base = kge_train_step_workspace_size(fn, nentity, nrelation, rel_ld, B, N, D);
+    if (base < 0) return -1;
+    return reg_ws_layout(nullptr, base, nentity, nrelation, rel_ld).bytes;
+}
+
+// kge_train_step (reg_entry false: weights required, no regulariser, no log, its own workspace size) and
+// kge_train_step_reg in one body. Every rejection comes before the first launch.
+static int train_step_impl(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld, float* rel,
+                           int64_t nrelation, int64_t rel_ld, int64_t rel_off, const int64_t* pos, const int64_t* neg,
+                           int64_t neg_ld, int64_t B, int64_t N, int64_t D, float gamma, float emb_range,
+                           float temperature, int adversarial, int detach, const float* weight, float* loss,
+                           float* loss_sum, float* out_neg, float* out_pos, float* m_ent, float* v_ent, float* m_rel,
+                           float* v_rel, float lr, float beta1, float beta2, float eps, int64_t step, int keras,
+                           void* workspace, int64_t workspace_bytes, void* stream, bool reg_entry,
+                           float regularization, float* log) {
     int rc = check_fn_mode(fn, mode);
     if (rc) return rc;
     if (fn == KGE_PROTATE) return fail(KGE_ENOTSUP, "kge_train_step: pRotatE uses kge_step_backward_adam");
     if (mode == KGE_SINGLE) return fail(KGE_EINVAL, "kge_train_step needs a negative mode (0 or 1)");
+    if (!(regularization >= 0.f) || std::isinf(regularization))
+        return fail(KGE_EINVAL, "kge_train_step_reg: regularization must be finite and >= 0");
     if (B <= 0 || N <= 0 || D <= 0 || nentity < 0 || nrelation < 0) return fail(KGE_EINVAL, "bad shape");
     if (step < 1) return fail(KGE_EINVAL, "step is 1-based");
-    if (!ent || !rel || !pos || !neg || !weight || !loss || !out_neg || !out_pos || !m_ent || !v_ent || !m_rel ||
-        !v_rel)
+    if (!ent || !rel || !pos || !neg || (!weight && !reg_entry) || !loss || !out_neg || !out_pos || !m_ent || !v_ent ||
+        !m_rel || !v_rel)
         return fail(KGE_EINVAL, "null pointer");
     if (B * N + 3 * B >= (int64_t)INT32_MAX || nentity >= (int64_t)INT32_MAX)
         return fail(KGE_EINVAL, "too many gradient events for 32-bit codes");
     const TrainWs t = train_ws_layout((char*)workspace, fn, nentity, nrelation, rel_ld, B, N, D);
-    if (!workspace || workspace_bytes < t.bytes) return fail(KGE_EINVAL, "workspace too small");
+    const RegWs rw = reg_ws_layout((char*)workspace, t.bytes, nentity, nrelation, rel_ld);
+    if (!workspace || workspace_bytes < (reg_entry ? rw.bytes : t.bytes))
+        return fail(KGE_EINVAL, "workspace too small");
+    // the finishing launch of the regulariser's value and the log; without it (kge_train_step; lambda 0 and no
+    // log) the step is launch for launch the plain one
+    const bool reg_finish = reg_entry && (regularization != 0.f || log);
     const int64_t base = kge_step_backward_workspace_size(fn, nentity, B, N, D);
     const StepWs w = step_ws_layout((char*)workspace, nentity, B, N, D, ent_width(fn, D), rel_width(fn, D));
     float* d_rel = (float*)((char*)workspace + base);
@@ -2040,6 +2180,16 @@ int kge_train_step(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld
     o.rel_p = rel;
     o.rel_m = m_rel;
     o.rel_v = v_rel;
+    o.reg = reg_entry ? regularization : 0.f;
+    o.reg_finish = reg_finish;
+    o.reg_part = rw.part;
+    o.reg_chunk = rw.chunk;
+    o.loss_parts = rw.loss_parts;
+    o.loss = loss;
+    o.loss_sum = loss_sum;  // with the finishing launch, the Sum metric advances there, by the loss with its term
+    o.log = log;
+    float* const parts = reg_finish ? rw.loss_parts : nullptr;
+    float* const sum_now = reg_finish ? nullptr : loss_sum;
 
     // 1. forward of both model calls (supervisor.py:17-18); phase 1 of the backward fused in where its
     //    accumulators fit, and the gradient events counted into their entity buckets
@@ -2071,8 +2221,8 @@ int kge_train_step(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld
         rc = run_score(fn, mode, p, fn == KGE_INTERHT ? KIND_STEP_FWD_STATS : KIND_STEP_FWD, stream);
         if (rc) return rc;
         hipLaunchKernelGGL(step_loss_kernel, dim3(1), dim3(kLossBlock), 0, st, out_neg, out_pos, weight, B, loss,
-                           t.d_out);
-        if (loss_sum) hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(1), 0, st, loss, loss_sum);
+                           t.d_out, parts);
+        if (sum_now) hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(1), 0, st, loss, sum_now);
         rc = check_launch("kge_train_step loss");
         if (rc) return rc;
         g.cand_stats = t.stats;
@@ -2114,7 +2264,8 @@ int kge_train_step(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld
     e.weight = weight;
     e.pos_raw = t.ps;
     e.loss = loss;
-    e.loss_sum = loss_sum;
+    e.loss_sum = sum_now;
+    e.loss_parts = parts;
     e.ev_cursor = w.cursor;
     e.ev_code_w = w.code;
     if (tiled) {
@@ -2127,6 +2278,31 @@ int kge_train_step(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld
     // 4. phase 2 with Adam fused into the entity pass, relation gradient with Adam (supervisor.py:25-26)
     o.dq_ready = o.epilogue_done = true;
     return step_backward_impl(tab, batch, g, workspace, base, stream, &a, m_ent, v_ent, o);
+}
+
+int kge_train_step(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld, float* rel, int64_t nrelation,
+                   int64_t rel_ld, int64_t rel_off, const int64_t* pos, const int64_t* neg, int64_t neg_ld, int64_t B,
+                   int64_t N, int64_t D, float gamma, float emb_range, float temperature, int adversarial, int detach,
+                   const float* weight, float* loss, float* loss_sum, float* out_neg, float* out_pos,
+                   float* m_ent, float* v_ent, float* m_rel, float* v_rel, float lr, float beta1, float beta2,
+                   float eps, int64_t step, int keras, void* workspace, int64_t workspace_bytes, void* stream) {
+    return train_step_impl(fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N, D,
+                           gamma, emb_range, temperature, adversarial, detach, weight, loss, loss_sum, out_neg,
+                           out_pos, m_ent, v_ent, m_rel, v_rel, lr, beta1, beta2, eps, step, keras, workspace,
+                           workspace_bytes, stream, false, 0.f, nullptr);
+}
+
+int kge_train_step_reg(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld, float* rel, int64_t nrelation,
+                       int64_t rel_ld, int64_t rel_off, const int64_t* pos, const int64_t* neg, int64_t neg_ld,
+                       int64_t B, int64_t N, int64_t D, float gamma, float emb_range, float temperature,
+                       int adversarial, int detach, const float* weight, float* loss, float* loss_sum, float* out_neg,
+                       float* out_pos, float* m_ent, float* v_ent, float* m_rel, float* v_rel, float lr, float beta1,
+                       float beta2, float eps, int64_t step, int keras, void* workspace, int64_t workspace_bytes,
+                       void* stream, float regularization, float* log) {
+    return train_step_impl(fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N, D,
+                           gamma, emb_range, temperature, adversarial, detach, weight, loss, loss_sum, out_neg,
+                           out_pos, m_ent, v_ent, m_rel, v_rel, lr, beta1, beta2, eps, step, keras, workspace,
+                           workspace_bytes, stream, true, regularization, log);
 }
 
 }  // extern "C"

@@ -2787,7 +2787,10 @@ __device__ __forceinline__ void ent_event(const ScoreParams& p, const Cand<FN, V
     }
 }
 
-template <int FN, bool CH, int V, int G>
+// REG: the L3 regulariser of kge_train_step_reg (p.reg3 != 0) joins the fused optimizer; a template parameter, so
+// the plain instances are the code they were (as a runtime branch it cost them 1-16 VGPRs,
+// profiles/r09_train_reg_resources.txt)
+template <int FN, bool CH, int V, int G, bool REG = false>
 __global__ __launch_bounds__(kBlock) void bwd_ent_kernel(ScoreParams p) {
     const int64_t e = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     if (e >= p.c_rows) return;
@@ -2848,6 +2851,24 @@ __global__ __launch_bounds__(kBlock) void bwd_ent_kernel(ScoreParams p) {
         float* prow = const_cast<float*>(p.cent) + e * p.c_ld;
         float* mrow = p.adam.m + e * p.c_ld;
         float* vrow = p.adam.v + e * p.c_ld;
+        if constexpr (REG) {
+            // L3 regulariser: 3 lambda x |x| joins the gradient of the row in registers, and the wave leaves its
+            // sum of |x|^3 (lanes past the width hold zeros)
+            float s3 = 0.f;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+#pragma unroll
+                for (int h = 0; h < NH; ++h)
+#pragma unroll
+                    for (int i = 0; i < V; ++i) {
+                        const float x = h ? c.cb[k].a[i] : c.ca[k].a[i];
+                        const float xa = x * fabsf(x);
+                        (h ? acc_b[k] : acc_a[k]).a[i] += p.reg3 * xa;
+                        s3 += fabsf(x) * fabsf(xa);
+                    }
+            s3 = wave_sum(s3);
+            if (lane == 0) p.reg_part[e] = s3;
+        }
 #pragma unroll
         for (int k = 0; k < G; ++k) {
             const int gi = lane + k * kWave;
@@ -3175,7 +3196,7 @@ __global__ __launch_bounds__(kBlock) void step_epilogue_kernel(ScoreParams p) {
         const int t = threadIdx.x;
         float sw = 0.f, sp = 0.f, sn = 0.f;
         for (int64_t i = t; i < B; i += kBlock) {
-            const float wi = p.weight[i];
+            const float wi = p.weight ? p.weight[i] : 1.f;  // no weights: uni_weight, plain means
             sw += wi;
             sp += wi * p.out_pos_ls[i];
             sn += wi * p.out_neg[i];
@@ -3197,6 +3218,10 @@ __global__ __launch_bounds__(kBlock) void step_epilogue_kernel(ScoreParams p) {
             const float loss = (-red[1][0] / tw + -red[2][0] / tw) / 2.f;
             *p.loss = loss;
             if (p.loss_sum) *p.loss_sum += loss;
+            if (p.loss_parts) {
+                p.loss_parts[0] = -red[1][0] / tw;
+                p.loss_parts[1] = -red[2][0] / tw;
+            }
         }
         return;
     }
@@ -3208,9 +3233,9 @@ __global__ __launch_bounds__(kBlock) void step_epilogue_kernel(ScoreParams p) {
         const int64_t b = negslot ? slot : (rowgrad ? slot - 2 * B : slot - B);
         // sum w in a fixed order: every wave gets the same value
         float sw = 0.f;
-        for (int64_t i = lane; i < B; i += kWave) sw += p.weight[i];
+        for (int64_t i = lane; i < B; i += kWave) sw += p.weight ? p.weight[i] : 1.f;
         sw = wave_sum(sw);
-        const float wb = p.weight[b];
+        const float wb = p.weight ? p.weight[b] : 1.f;
         const float go = (-0.5f / sw) * wb;
         if (rowgrad) {
             neg_row_bwd(p.neg_scores + b * p.ns_ld, p.N, p.temperature, p.adversarial, p.detach, go,
@@ -3342,7 +3367,7 @@ constexpr int kEntSortMax = 2048;
 // the relation row, is read from the relation table instead: it stays in L2)
 constexpr int ent_nq(int fn) { return (fn == KGE_COMPLEX || fn == KGE_ROTATE || fn == KGE_INTERHT) ? 2 : 1; }
 
-template <int FN, bool CH, int V, int G>
+template <int FN, bool CH, int V, int G, bool REG = false>  // REG: as bwd_ent_kernel's
 __global__ __launch_bounds__(kBlock) void bwd_ent_stream_kernel(ScoreParams p) {
     static_assert(G % kWavesPerBlock == 0, "the streaming phase 2 needs a multiple of 4 groups per lane");
     constexpr int GW = G / kWavesPerBlock;
@@ -3585,6 +3610,24 @@ __global__ __launch_bounds__(kBlock) void bwd_ent_stream_kernel(ScoreParams p) {
     if (n <= 0) load_mv();
     auto sstore = [&](rsrc_t r, uint32_t off, const vecf<V>& v) { bstore<V, kEntStAux>(r, off, v); };
     if (p.adam.on) {
+        if constexpr (REG) {
+            // L3 regulariser (no barrier): 3 lambda x |x| joins the gradient of the slice in registers, and each
+            // wave leaves its own sum of |x|^3 (lanes past the width hold zeros)
+            float s3 = 0.f;
+#pragma unroll
+            for (int gg = 0; gg < GW; ++gg)
+#pragma unroll
+                for (int h = 0; h < NH; ++h)
+#pragma unroll
+                    for (int i = 0; i < V; ++i) {
+                        const float x = h ? cb[gg].a[i] : ca[gg].a[i];
+                        const float xa = x * fabsf(x);
+                        (h ? sb[gg] : sa[gg]).a[i] += p.reg3 * xa;
+                        s3 += fabsf(x) * fabsf(xa);
+                    }
+            s3 = wave_sum(s3);
+            if (lane == 0) p.reg_part[e * kWavesPerBlock + w] = s3;
+        }
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
             const rsrc_t sp = make_rsrc(p.cent + e * p.c_ld + h * D, nb);
@@ -3768,15 +3811,31 @@ void launch_tile(const ScoreParams& p, hipStream_t st, int blocks) {
         }                                              \
         return false;                                  \
     }
+// phase 2: the plain instance, or the one with the L3 regulariser (kge_train_step_reg with lambda != 0; it refuses
+// pRotatE, which has no such instance)
+#define KGE_KIND_REG(K, kernel)                        \
+    if (kind == K) {                                   \
+        if constexpr (kind_has(K, FN, CH, G)) {        \
+            if (p.reg3 == 0.f) {                       \
+                KGE_LAUNCH(kernel, FN, CH, V, G);      \
+                return true;                           \
+            }                                          \
+            if constexpr (FN != KGE_PROTATE) {         \
+                KGE_LAUNCH(kernel, FN, CH, V, G, true); \
+                return true;                           \
+            }                                          \
+        }                                              \
+        return false;                                  \
+    }
 template <int FN, bool CH, int V, int G>
 bool launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
     if (kind == KIND_SHARD_FWD_GRAD || kind == KIND_SHARD_POS || kind == KIND_SHARD_EPILOGUE)
         return launch_shard<FN, CH, V, G>(p, kind, st, blocks);
     KGE_KIND(KIND_BWD, score_bwd_kernel, FN, CH, V, G)
     KGE_KIND(KIND_BWD_ROWS, bwd_rows_kernel, FN, CH, V, G)
-    KGE_KIND(KIND_BWD_ENT, bwd_ent_kernel, FN, CH, V, G)
+    KGE_KIND_REG(KIND_BWD_ENT, bwd_ent_kernel)
+    KGE_KIND_REG(KIND_BWD_ENT_STREAM, bwd_ent_stream_kernel)
     KGE_KIND(KIND_BWD_STREAM, bwd_stream_kernel, FN, CH, V, G)
-    KGE_KIND(KIND_BWD_ENT_STREAM, bwd_ent_stream_kernel, FN, CH, V, G)
     KGE_KIND(KIND_BWD_CHAIN, bwd_chain_kernel, FN, CH, V, G)
     KGE_KIND(KIND_FWD_STATS, score_fwd_kernel, FN, CH, V, G, true)
     KGE_KIND(KIND_STEP_FWD, step_fwd_kernel, FN, CH, V, G, false)
@@ -3830,6 +3889,7 @@ bool launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
     return false;
 }
 #undef KGE_KIND
+#undef KGE_KIND_REG
 
 template <int FN, bool CH, int V>
 int launch_g(const ScoreParams& p, int kind, hipStream_t st, int blocks, int G) {

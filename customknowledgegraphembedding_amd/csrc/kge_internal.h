@@ -305,6 +305,10 @@ struct ScoreParams {
         float b1, b2, eps, alpha, step_size, bc2_sqrt;
         int keras, on;
     } adam;
+    float* loss_parts;  // [2] epilogue: positive_sample_loss, negative_sample_loss (kge_train_step_reg; may be null)
+    // L3 ("N3") regulariser in phase 2 (kge_train_step_reg). reg3 == 0: off, the plain instances run.
+    float reg3;       // 3 lambda: every element x of row e gets reg3 x |x| added to its gradient before Adam
+    float* reg_part;  // sum |x|^3 of what each wave holds: [E] (bwd_ent_kernel), [E, 4] (bwd_ent_stream_kernel)
 };
 
 // Adam coefficients of step t (1-based), computed on the host in double

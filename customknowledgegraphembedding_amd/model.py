@@ -139,6 +139,39 @@ class _KGEBase(nn.Module):
         return (f"model_name={self.model_name}, nentity={self.nentity}, nrelation={self.nrelation}, "
                 f"entity_dim={self.entity_dim}, relation_dim={self.relation_dim}, gamma={self._gamma_f}")
 
+    # shared by the fused train steps of both classes (kge_train_step, kge_train_step_reg)
+    def _train_workspace(self, nbytes, device):
+        """kge_train_step's workspace, cached by size (the call zeroes the counters it keeps there
+        itself, so the contents never matter: any shape may reuse a large-enough buffer)."""
+        ws = getattr(self, "_train_ws", None)
+        if ws is None or ws.numel() < nbytes or ws.device != device:
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+            self._train_ws = ws
+        return ws
+
+    def _adam_state(self, optimizer, params):
+        """(group, lr, step) for the next update. The step counters are NOT advanced here: the caller
+        commits them with _adam_commit only after the kernel call returned success, so a rejected
+        call leaves the bias correction where it was."""
+        from .optim import resolve_lr
+
+        group = optimizer.param_groups[0]
+        st0 = optimizer.state[self.entity_embedding]
+        lr = resolve_lr(group["lr"], st0["step"] if st0 else 0)
+        for prm in params:
+            st = optimizer.state[prm]
+            if not st:
+                st["step"] = 0
+                st["exp_avg"] = ops.like_strided(prm, zero=True)
+                st["exp_avg_sq"] = ops.like_strided(prm, zero=True)
+            check_adam_moments(prm, st)
+        return group, lr, optimizer.state[self.entity_embedding]["step"] + 1
+
+    @staticmethod
+    def _adam_commit(optimizer, params):
+        for prm in params:
+            optimizer.state[prm]["step"] += 1
+
 
 class TFKGEModel(_KGEBase):
     """Drop-in for ``TFKGEModel`` (tensorflow_codes/model.py:47-235)."""
@@ -224,16 +257,6 @@ class TFKGEModel(_KGEBase):
                                     modulus=modulus, temperature=1.0, adversarial=True, detach=False)
         return neg.unsqueeze(1), pos.unsqueeze(1)
 
-
-    def _train_workspace(self, nbytes, device):
-        """kge_train_step's workspace, cached by size (the call zeroes the counters it keeps there
-        itself, so the contents never matter: any shape may reuse a large-enough buffer)."""
-        ws = getattr(self, "_train_ws", None)
-        if ws is None or ws.numel() < nbytes or ws.device != device:
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-            self._train_ws = ws
-        return ws
-
     def train_step_fused(self, positive_sample, negative_sample, subsampling_weight, mode, optimizer,
                          one_call=True, loss_sum=None):
         """supervisor.py:15-26 entirely in HIP. Needs `optimizer` =
@@ -301,29 +324,6 @@ class TFKGEModel(_KGEBase):
         _lib.check(rc, "kge_step_backward_adam")
         self._adam_commit(optimizer, [ent, rel] + ([self.modulus] if is_p else []))
         return loss.detach()
-
-    def _adam_state(self, optimizer, params):
-        """(group, lr, step) for the next update. The step counters are NOT advanced here: the caller
-        commits them with _adam_commit only after the kernel call returned success, so a rejected
-        call leaves the bias correction where it was."""
-        from .optim import resolve_lr
-
-        group = optimizer.param_groups[0]
-        st0 = optimizer.state[self.entity_embedding]
-        lr = resolve_lr(group["lr"], st0["step"] if st0 else 0)
-        for prm in params:
-            st = optimizer.state[prm]
-            if not st:
-                st["step"] = 0
-                st["exp_avg"] = ops.like_strided(prm, zero=True)
-                st["exp_avg_sq"] = ops.like_strided(prm, zero=True)
-            check_adam_moments(prm, st)
-        return group, lr, optimizer.state[self.entity_embedding]["step"] + 1
-
-    @staticmethod
-    def _adam_commit(optimizer, params):
-        for prm in params:
-            optimizer.state[prm]["step"] += 1
 
     def _train_step_one_call(self, fn, m, positive_sample, negative_sample, subsampling_weight, optimizer,
                              loss_sum=None):
@@ -449,6 +449,64 @@ class KGEModel(_KGEBase):
             "negative_sample_loss": negative_sample_loss.item(),
             "loss": loss.item(),
         }
+        return log
+
+    @staticmethod
+    def train_step_fused(model, optimizer, train_iterator, args):
+        """``train_step``'s signature and log in one kge_train_step_reg call: forward, upstream's loss with its
+        flags (``uni_weight``, ``negative_adversarial_sampling`` / ``adversarial_temperature`` with detached
+        weights, the L3 ``regularization``), deterministic backward and Adam, no dense gradient table.
+        ``optimizer`` must be this package's ``optim.Adam`` (either ``semantics``) over the model's parameters,
+        else TypeError; an Adam moment laid out unlike its parameter is a ValueError (check_adam_moments) before
+        anything is launched. pRotatE has no such step: NotImplementedError, use ``train_step``. The log's four
+        values come back in one device-to-host copy."""
+        from .optim import Adam
+        from . import _lib
+
+        if not isinstance(optimizer, Adam):
+            raise TypeError("train_step_fused needs customknowledgegraphembedding_amd.optim.Adam")
+        if model.model_name == "pRotatE":
+            raise NotImplementedError("pRotatE has no fused train step (kge_train_step_reg); use KGEModel.train_step")
+        model.train()
+        positive_sample, negative_sample, subsampling_weight, mode = next(train_iterator)
+        ent, rel = model.entity_embedding, model.relation_embedding
+        dev = ent.device
+        pos = positive_sample.to(dev, non_blocking=True).contiguous()
+        neg = negative_sample.to(dev, non_blocking=True)
+        if neg.stride(1) != 1:
+            neg = neg.contiguous()
+        w = None
+        if not args.uni_weight:
+            w = subsampling_weight.to(dev, non_blocking=True).reshape(-1).to(torch.float32).contiguous()
+        ops._need_gpu(ent, pos, neg)
+        for prm in (ent, rel):
+            if optimizer.state[prm]:
+                check_adam_moments(prm, optimizer.state[prm])
+        adv = bool(args.negative_adversarial_sampling)
+        temp = float(args.adversarial_temperature) if adv else 1.0
+        reg = float(args.regularization)
+        fn, m = FN_IDS[model.model_name], ops.mode_id(mode)
+        B, N = neg.shape
+        group, lr, step = model._adam_state(optimizer, [ent, rel])
+        b1, b2 = group["betas"]
+        lib = _lib.load()
+        nbytes = lib.kge_train_step_reg_workspace_size(fn, ent.shape[0], rel.shape[0], rel.stride(0), B, N, model._D)
+        ws = model._train_workspace(nbytes, dev)
+        out = torch.empty(2 * B + 5, dtype=torch.float32, device=dev)  # log[4] | loss | out_neg | out_pos
+        rc = lib.kge_train_step_reg(
+            fn, m, ent.data_ptr(), ent.shape[0], ent.stride(0), rel.data_ptr(), rel.shape[0], rel.stride(0),
+            model._rel_off, pos.data_ptr(), neg.data_ptr(), neg.stride(0), B, N, model._D, model._gamma_f,
+            model._range_f, temp, int(adv), 1, None if w is None else w.data_ptr(), out[4:].data_ptr(), None,
+            out[5:].data_ptr(), out[5 + B:].data_ptr(),
+            optimizer.state[ent]["exp_avg"].data_ptr(), optimizer.state[ent]["exp_avg_sq"].data_ptr(),
+            optimizer.state[rel]["exp_avg"].data_ptr(), optimizer.state[rel]["exp_avg_sq"].data_ptr(),
+            float(lr), float(b1), float(b2), float(group["eps"]), int(step), int(group["semantics"] == "keras"),
+            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream, reg, out.data_ptr())
+        _lib.check(rc, "kge_train_step_reg")
+        model._adam_commit(optimizer, [ent, rel])
+        loss, pos_loss, neg_loss, reg_term = out[:4].tolist()
+        log = {"regularization": reg_term} if reg != 0.0 else {}
+        log.update(positive_sample_loss=pos_loss, negative_sample_loss=neg_loss, loss=loss)
         return log
 
 
