@@ -760,7 +760,9 @@ int tile_plan(int fn, ScoreParams& p, const kge_forms* forms = nullptr) {
     if (forms && forms->tile_q2slots >= 0) QS = std::min<int64_t>(QS, forms->tile_q2slots);
 #ifdef KGE_PROFILING_KNOBS
     // profiling-only A/B knobs (a build with -DKGE_PROFILING_KNOBS): KGE_TILE_DRY=<level> runs the setup alone and
-    // writes no scores; KGE_TILE_NOSORT keeps the batch-row order
+    // writes no scores (unplanned: 1 = the rows' ids, 2 = + the query build, 3 = + the bucket counts, 4 = the whole
+    // setup; a planned step: 1 = the prologue's first round trip, the plan's header, bounds and rows; 2 and above =
+    // the whole prologue, through its one barrier); KGE_TILE_NOSORT keeps the batch-row order
     p.tile_dry = getenv("KGE_TILE_DRY") ? std::max(1, atoi(getenv("KGE_TILE_DRY"))) : 0;
     if (getenv("KGE_TILE_NOSORT")) P2 = 0;
 #endif
@@ -1194,8 +1196,8 @@ int kge_step_planner_get(const kge_step_planner* sp, int what) {
 int kge_step_planner_set_clocks(kge_step_planner* sp, void* clocks, int64_t clocks_bytes) {
 #ifdef KGE_PROFILING_KNOBS
     if (!sp) return fail(KGE_EINVAL, "kge_step_planner_set_clocks: null pointer");
-    if (clocks && (clocks_bytes < sp->groups * 8 * kSweepClkMarks * 8 || !aligned(clocks, 8)))
-        return fail(KGE_EINVAL, "kge_step_planner_set_clocks: 8 * groups * 48 bytes, 8-B aligned");
+    if (clocks && (clocks_bytes < kge_sweep_clk_words(sp->groups) * 8 || !aligned(clocks, 8)))
+        return fail(KGE_EINVAL, "kge_step_planner_set_clocks: groups * (8 * 40 + 2) * 8 bytes, 8-B aligned");
     sp->clk = reinterpret_cast<long long*>(clocks);
     return ok();
 #else

@@ -946,6 +946,11 @@ step_fwd_xcd_kernel(ScoreParams p) {
 //      kSweepBoardInts): wave 0 publishes the entity bucket it has reached, and a wave naps once before an item
 //      that leads another block of its slice by more than p.tile_lead buckets, so the slice's blocks stay inside
 //      one L2 window. No wait depends on the board; the scores do not depend on DEPTH or the board.
+// A planned step (PLANNED instances) takes the rows, the checked ids and the sorted items from its plan instead of
+// steps 1-2's id work: round trip 1 reads the plan's header, the slice's bounds and the rows (each wave the rows it
+// builds, and all rows of the group in its lanes); round trip 2 holds, all in flight together, the wave's first list
+// entries, the relation thirds of the runs it fills (each wave ranks the runs itself by ballot) and its rows' query
+// operands; then the images are written and ONE barrier precedes the sweep.
 // The block sweeps its slice in ONE ascending front, and the ~32 blocks of an XCD sweep the same slice
 // together, so the ~3.4 gathers of an entity row (C2) are issued by one XCD close in time and the repeats
 // hit its L2. Against step_fwd_xcd_kernel (one wave per (row, slice, phase), which rebuilds its row's query
@@ -1169,10 +1174,17 @@ __global__ __launch_bounds__(NWV * kWave) void tile_plan_kernel(PlanArgs a) {
     tile_plan_group<NWV>(a, (int)blockIdx.x, reinterpret_cast<int*>(plan_smem));
 }
 
-template <int FN, bool CH, int V, int G, int NWV, int DEPTH>
+// PLANNED: the instances of a planned step (p.tile_plan; launch_tile chooses): rows, ids and sorted items come from
+// the plan, and steps 0-2 below are replaced by the planned prologue. BOARD (planned only): the lead throttle; an
+// instance without it holds none of the board's instructions.
+template <int FN, bool CH, int V, int G, int NWV, int DEPTH, bool PLANNED = false, bool BOARD = false>
 __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams p) {
     static_assert(DEPTH == 1 || DEPTH == 2, "candidate rows in flight per wave");
+    static_assert(PLANNED || !BOARD, "the board belongs to a planned step");
     extern __shared__ __attribute__((aligned(16))) unsigned char tile_smem[];
+#ifdef KGE_PROFILING_KNOBS
+    const long long clk_entry = wall_clock64();
+#endif
     constexpr int NQ = tile_nq(FN);
     constexpr int W = G * kWave;
     constexpr int NT = NWV * kWave;
@@ -1187,25 +1199,59 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
     int* cntp = hist + kTileBuckets;
     int* list = cntp + 4;  // also the relation sort's keys before the list is built
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (p.tile_next.plan && (int)blockIdx.x >= p.tile_blocks) {
-        // a tail block: the NEXT batch's plan, on the CUs the scoring blocks free up at the end of the launch
-        tile_plan_group<NWV>(p.tile_next, (int)blockIdx.x - p.tile_blocks, reinterpret_cast<int*>(tile_smem));
-        return;
+    if constexpr (PLANNED) {
+        if (p.tile_next.plan && (int)blockIdx.x >= p.tile_blocks) {
+            // a tail block: the NEXT batch's plan, on the CUs the scoring blocks free up at the end of the launch
+            tile_plan_group<NWV>(p.tile_next, (int)blockIdx.x - p.tile_blocks, reinterpret_cast<int*>(tile_smem));
+#ifdef KGE_PROFILING_KNOBS
+            if (p.tile_clk && t == 0) {  // (kge_internal.h: the clock record) the plan block's entry and thread 0's exit
+                long long* const pc = p.tile_clk + (int64_t)p.tile_blocks * kSweepClkMarks + 2 * ((int)blockIdx.x - p.tile_blocks);
+                pc[0] = clk_entry;
+                pc[1] = wall_clock64();
+            }
+#endif
+            return;
+        }
     }
     const int x = (int)(blockIdx.x & 7);
     const int gi = (int)(blockIdx.x >> 3);
     const int64_t g0 = (int64_t)gi * R;
     const int nr = (int)min<int64_t>(R, p.B - g0);
     if (nr <= 0) return;  // block-uniform
-    // a planned step (kge_step_forward_planned): rows, ids and this block's sorted items come from the plan
-    const int* pl = p.tile_plan;
-    const int4* pmeta = pl ? reinterpret_cast<const int4*>(pl + kPlanHdr) + (int64_t)gi * R : nullptr;
-    const int2* plist = pl ? reinterpret_cast<const int2*>(pl + plan_list(p.B, R)) + (int64_t)gi * R * (p.N + 1) : nullptr;
-    int plo = 0, pcnt = 0;
-    if (pl) {
+    const int64_t S = (p.c_rows + 7) / 8;
+    const int64_t e_lo = min((int64_t)x * S, p.c_rows), e_hi = min(p.c_rows, e_lo + S);
+    // column N: the row's positive (its tail) in tail-batch mode, where it shares the negatives' query; head-batch
+    // positives need their own (h, r) query and are scored after the sweep
+    const int64_t Np = (p.tile_pos && !CH) ? p.N + 1 : p.N;
+    const float bscale = (float)kTileBuckets / (float)S;
+    int cnt = 0;  // the block's items
+    // a planned step: this block's segment of the plan's sorted list as a buffer (a read at or past its cnt entries
+    // returns 0), each wave's first entries (loaded in the prologue), and the group's rows in the plan
+    [[maybe_unused]] rsrc_t prs = make_rsrc(nullptr, 0u);
+    [[maybe_unused]] int pre_id = 0, pre_code = 0;
+    [[maybe_unused]] const int4* pmeta = nullptr;
+
+    if constexpr (PLANNED) {
+        // The planned prologue (kge_step_forward_planned): rows, ids and this block's sorted items come from the
+        // plan, so the setup is two global round trips and one barrier before the first candidate rows.
+        // KGE_TILE_DRY levels here: 1 = round trip 1 alone; 2 and 3 = through the barrier (the whole prologue).
+        const int* pl = p.tile_plan;
+        pmeta = reinterpret_cast<const int4*>(pl + kPlanHdr) + (int64_t)gi * R;
+        const int2* plist = reinterpret_cast<const int2*>(pl + plan_list(p.B, R)) + (int64_t)gi * R * (p.N + 1);
+        // round trip 1: the header, the slice's bounds, the rows this wave builds (A: row w; B: row w + NWV where
+        // the block has fewer waves than rows) and, lane r, row r of the group (the relation runs; wave 0 also puts
+        // the rows' ids into LDS for the sweep). The plan holds R rows per group, -1 past the batch.
+        constexpr bool TWO = NWV < kTileMaxRows;
+        const int* so = pl + plan_soff(p.B, R) + (int64_t)gi * 9;
+        const bool hasA = w < nr, hasB = TWO && w + NWV < nr;
+        const int rA = hasA ? w : 0, rB = hasB ? w + NWV : rA;
+        const int h0 = pl[0], h1 = pl[1], h2 = pl[2], h3 = pl[3], h4 = pl[4], h5 = pl[5], h6 = pl[6];
+        const int plo = so[x], phi = so[x + 1];
+        const int4 mA = pmeta[rA], mB = pmeta[rB];
+        const int4 ml = pmeta[min(lane, R - 1)];
         const int mode = CH ? KGE_HEAD_BATCH : KGE_TAIL_BATCH;
-        if (pl[0] != kPlanMagic || pl[1] != (int)p.B || pl[2] != (int)p.N || pl[3] != mode || pl[4] != R ||
-            pl[5] != (int)p.c_rows || (pl[6] != 0) != (p.tile_sort != 0)) {
+        if (h0 != kPlanMagic || h1 != (int)p.B || h2 != (int)p.N || h3 != mode || h4 != R || h5 != (int)p.c_rows ||
+            (h6 != 0) != (p.tile_sort != 0)) {
             // not this batch shape's plan (or a plan made for a score function with the other row order): every
             // output of the block's rows (by index) becomes NaN, loudly. A plan of the same shape made from other
             // ids is not detectable here: kge_step_planner_* (ops.StepPlanner) pairs plans with batches
@@ -1219,259 +1265,321 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
                 }
             return;
         }
-        const int* so = pl + plan_soff(p.B, R) + (int64_t)gi * 9;
-        plo = so[x];
-        pcnt = so[x + 1] - plo;
-    }
-    const int64_t S = (p.c_rows + 7) / 8;
-    const int64_t e_lo = min((int64_t)x * S, p.c_rows), e_hi = min(p.c_rows, e_lo + S);
-    // column N: the row's positive (its tail) in tail-batch mode, where it shares the negatives' query; head-batch
-    // positives need their own (h, r) query and are scored after the sweep
-    const int64_t Np = (p.tile_pos && !CH) ? p.N + 1 : p.N;
+        cnt = max(phi - plo, 0);
+        const bool inl = lane < nr;
+        const int relv = (inl && ml.z >= 0 && ml.z < p.r_rows) ? ml.z : -1;  // lane r: row r's checked relation id
+        if (w == 0 && inl) {
+            brow[lane] = ml.x;
+            qid[lane] = CH ? ml.w : ml.y;
+            rrow[lane] = relv;
+        }
+        if (p.tile_dry == 1) return;
+        // round trip 2, everything issued before anything waits: the wave's first list entries, the relation thirds
+        // of the runs it fills, its rows' query operands
+        prs = make_rsrc(plist + plo, (uint32_t)cnt * 8u);
+        {
+            const int ci = p.tile_rev ? cnt - 1 - (w + NWV * lane) : w + NWV * lane;
+            const auto e = __builtin_amdgcn_raw_buffer_load_b64(prs, (uint32_t)((ci >= 0 && ci < cnt) ? ci : cnt) * 8u, 0, 0);
+            pre_id = (int)e[0];
+            pre_code = (int)e[1];
+        }
+        // InterHT relation slots: one per run of equal relations among the block's rows (first QS runs; the rows of
+        // later runs read their relation third from the table per candidate). Every wave ranks the runs itself from
+        // the relation ids in its lanes; the run's first row's wave fills the slot
+        [[maybe_unused]] vecf<V> t2a[G], t2b[G];
+        [[maybe_unused]] int slA = -1, slB = -1;
+        if constexpr (FN == KGE_INTERHT) {
+            static_assert(kTileMaxRows <= kWave, "one lane per row");
+            const int prev = __shfl_up(relv, 1, kWave);
+            const bool open = inl && (lane == 0 || relv != prev);
+            const uint64_t m = __ballot(open);
+            const int sl = __popcll(m & (lane == 63 ? ~0ull : (2ull << lane) - 1)) - 1;
+            const int slv = (inl && sl < QS) ? sl : -1;
+            if (w == 0 && inl) q2slot[lane] = slv;
+            auto third = [&](int r, bool has, int& slot, vecf<V>* t2) {
+                const int s = __builtin_amdgcn_readlane(slv, r);
+                const int sp = __builtin_amdgcn_readlane(slv, r > 0 ? r - 1 : 0);
+                const int ri = __builtin_amdgcn_readlane(relv, r);
+                slot = (has && s >= 0 && !(r > 0 && sp == s)) ? s : -1;
+                const rsrc_t sr = make_rsrc(p.rel + (ri >= 0 ? ri : 0) * p.r_ld + p.r_off,
+                                            (slot >= 0 && ri >= 0) ? (uint32_t)p.D * 4u : 0u);
+#pragma unroll
+                for (int k = 0; k < G; ++k) t2[k] = bload<V>(sr, goff<V>(lane, k));
+            };
+            third(rA, hasA, slA, t2a);
+            if constexpr (TWO) third(rB, hasB, slB, t2b);
+        }
+        auto build_m = [&](const int4& m, bool has, Query<FN, CH, V, G>& q) {
+            const int64_t qi = CH ? m.w : m.y, ri = m.z;
+            const bool qok = has && qi >= 0 && qi < p.q_rows, rok = has && ri >= 0 && ri < p.r_rows;
+            q.build(p.qent + (qok ? qi : 0) * p.q_ld, qok, p.rel + (rok ? ri : 0) * p.r_ld + p.r_off, rok, p.D, lane, p);
+        };
+        auto put_q = [&](int r, const Query<FN, CH, V, G>& q) {
+            vecf<V>* qr = qimg + (size_t)r * NQ * W;
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                qr[lane + k * kWave] = q.q0[k];
+                if constexpr (NQ > 1) qr[W + lane + k * kWave] = q.q1[k];
+            }
+        };
+        {
+            Query<FN, CH, V, G> qa, qb;
+            build_m(mA, hasA, qa);
+            if constexpr (TWO) build_m(mB, hasB, qb);
+            if (hasA) put_q(rA, qa);
+            if constexpr (TWO) {
+                if (hasB) put_q(rB, qb);
+            }
+        }
+        if constexpr (FN == KGE_INTERHT) {
+            if (slA >= 0) {
+#pragma unroll
+                for (int k = 0; k < G; ++k) q2img[(size_t)slA * W + lane + k * kWave] = t2a[k];
+            }
+            if constexpr (TWO) {
+                if (slB >= 0) {
+#pragma unroll
+                    for (int k = 0; k < G; ++k) q2img[(size_t)slB * W + lane + k * kWave] = t2b[k];
+                }
+            }
+        }
+        __syncthreads();
+    } else {
+        // 0. the block's batch rows: ranks [g0, g0 + nr) of the batch in (relation, row) order (p.tile_sort: InterHT,
+        //    so that a block's rows share few relations and their relation thirds fit QS LDS slots), else rows g0 + r.
+        //    A stable counting sort over kTileSortRel relation buckets: row i = (u NWV + w) 64 + lane is ranked inside
+        //    its wave by ballots (one per distinct bucket of the wave), then by the bucket counts of the earlier waves.
+        if (p.tile_sort) {
+            constexpr int MU = (kTileSortMaxB + NT - 1) / NT, NB = kTileSortRel;
+            int* wc = list;  // [MU NWV][NB] per-wave bucket counts, then their exclusive prefixes
+            int bk[MU], wr[MU];
+            int64_t rv[MU], qv[MU];
+#pragma unroll
+            for (int u = 0; u < MU; ++u) {
+                const int i = u * NT + t;
+                bk[u] = NB;
+                rv[u] = qv[u] = 0;
+                if (i < p.B) {
+                    const int64_t rr = p.r_idx ? p.r_idx[i * p.r_stride] : i;
+                    rv[u] = rr;
+                    qv[u] = p.q_idx ? p.q_idx[i * p.q_stride] : i;
+                    bk[u] = (rr >= 0 && rr < p.r_rows) ? (int)min<int64_t>(rr, NB - 2) : NB - 1;
+                }
+            }
+            for (int i = t; i < MU * NWV * NB; i += NT) wc[i] = 0;
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < MU; ++u) {
+                wr[u] = 0;
+                if (u * NT >= p.B) continue;  // block-uniform
+                uint64_t todo = __ballot(bk[u] < NB);
+                while (todo) {  // wave-uniform: one round per distinct bucket of the wave
+                    const int v = __builtin_amdgcn_readlane(bk[u], __builtin_ctzll(todo));
+                    const uint64_t m = __ballot(bk[u] == v);
+                    if (bk[u] == v) wr[u] = lanes_below(m);
+                    if (lane == 0) wc[(u * NWV + w) * NB + v] = __popcll(m);
+                    todo &= ~m;
+                }
+            }
+            __syncthreads();
+            if (w == 0) {  // bucket v = lane: prefix over the waves in row order, then over the buckets
+                // (the counts are loaded all together and summed in registers: a dependent LDS round trip per wave
+                // slot cost ~1.5 us of the block's setup)
+                int y[MU * NWV];
+#pragma unroll
+                for (int c = 0; c < MU * NWV; ++c) y[c] = wc[c * NB + lane];
+                int run = 0;
+#pragma unroll
+                for (int c = 0; c < MU * NWV; ++c) {
+                    const int v = y[c];
+                    y[c] = run;
+                    run += v;
+                }
+                int incl = run;
+#pragma unroll
+                for (int o = 1; o < kWave; o <<= 1) {
+                    const int v = __shfl_up(incl, o, kWave);
+                    if (lane >= o) incl += v;
+                }
+                const int base = incl - run;
+#pragma unroll
+                for (int c = 0; c < MU * NWV; ++c) wc[c * NB + lane] = y[c] + base;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < MU; ++u) {
+                if (bk[u] >= NB) continue;
+                const int64_t rank = wc[(u * NWV + w) * NB + bk[u]] + wr[u];
+                if (rank >= g0 && rank < g0 + nr) {
+                    brow[rank - g0] = u * NT + t;
+                    qid[rank - g0] = qv[u];
+                    rrow[rank - g0] = rv[u];
+                }
+            }
+        } else if (t < nr) {
+            const int64_t b = g0 + t;
+            brow[t] = b;
+            qid[t] = p.q_idx ? p.q_idx[b * p.q_stride] : b;
+            rrow[t] = p.r_idx ? p.r_idx[b * p.r_stride] : b;
+        }
+        __syncthreads();
+        if (p.tile_dry == 1) return;  // A/B knob KGE_TILE_DRY=<level>: the setup up to this point alone
 
-    // 0. the block's batch rows: ranks [g0, g0 + nr) of the batch in (relation, row) order (p.tile_sort: InterHT,
-    //    so that a block's rows share few relations and their relation thirds fit QS LDS slots), else rows g0 + r.
-    //    A stable counting sort over kTileSortRel relation buckets: row i = (u NWV + w) 64 + lane is ranked inside
-    //    its wave by ballots (one per distinct bucket of the wave), then by the bucket counts of the earlier waves.
-    if (pl) {
-        if (t < nr) {
-            const int4 m = pmeta[t];
-            brow[t] = m.x;
-            qid[t] = CH ? m.w : m.y;
-            rrow[t] = m.z;
-        }
-    } else if (p.tile_sort) {
-        constexpr int MU = (kTileSortMaxB + NT - 1) / NT, NB = kTileSortRel;
-        int* wc = list;  // [MU NWV][NB] per-wave bucket counts, then their exclusive prefixes
-        int bk[MU], wr[MU];
-        int64_t rv[MU], qv[MU];
+        // 2. counting sort of the block's items of slice x by entity bucket
+        const int64_t nf = (int64_t)nr * Np;
+        // no 64-bit divisions in the walk (an emulated int64 divide is ~100 instructions): the item's row by a
+        // float reciprocal corrected to the exact quotient (f < R (N + 1) < 2^21), the entity bucket by a float
+        // scale (any monotone map of the slice onto the buckets orders the sweep)
+        const int Np32 = (int)Np;
+        const float inv_np = 1.f / (float)Np32;
+        auto item = [&](int64_t f64, int& bucket, int& code) -> bool {
+            const int f = (int)f64;
+            int r = (int)((float)f * inv_np);
+            if (r * Np32 > f) --r;
+            if ((r + 1) * Np32 <= f) ++r;
+            const int n = f - r * Np32;
+            const int64_t b = brow[r];
+            const int64_t id = n < p.N ? p.c_idx[b * p.c_stride + n] : p.pos_base[b * 3 + 2];
+            const int64_t row = id - p.c_base;
+            const bool valid = row >= 0 && row < p.c_rows;
+            if (valid ? (row < e_lo || row >= e_hi) : x != 0) return false;
+            bucket = valid ? min(kTileBuckets - 1, (int)((float)(int)(row - e_lo) * bscale)) : 0;
+            code = (r << 16) | n;
+            return true;
+        };
+        // the ids are loaded once, all in flight together, when the block's walk fits TPI per thread (C2: 4 112
+        // items over 768 threads); otherwise the walk is made twice (count, then scatter)
+        // 17 at 16 waves: a 16-row block's 16 x 1 025 tail-batch items at N = 1 024 (C4) over 1 024 threads, walked
+        // once (C4 tail-batch 94.5 -> 88 us); 16 at fewer waves, where the 17th slot measured ~1 us slower at C3
+        constexpr int TPI = NWV >= 16 ? 17 : 16;
+        int wbk[TPI], wcd[TPI];
+        const bool in_regs = nf <= (int64_t)TPI * NT;  // block-uniform
+        // (their loads are issued here, before the query build, so both latencies overlap)
+        if (in_regs) {
 #pragma unroll
-        for (int u = 0; u < MU; ++u) {
-            const int i = u * NT + t;
-            bk[u] = NB;
-            rv[u] = qv[u] = 0;
-            if (i < p.B) {
-                const int64_t rr = p.r_idx ? p.r_idx[i * p.r_stride] : i;
-                rv[u] = rr;
-                qv[u] = p.q_idx ? p.q_idx[i * p.q_stride] : i;
-                bk[u] = (rr >= 0 && rr < p.r_rows) ? (int)min<int64_t>(rr, NB - 2) : NB - 1;
+            for (int u = 0; u < TPI; ++u) {
+                const int64_t f = (int64_t)u * NT + t;
+                wbk[u] = -1;
+                if (f < nf && !item(f, wbk[u], wcd[u])) wbk[u] = -1;
             }
         }
-        for (int i = t; i < MU * NWV * NB; i += NT) wc[i] = 0;
+
+        // 1. the rows' query operands; with fewer waves than rows, two rows per wave built side by side (branch-free:
+        //    both rows' loads in flight together). The ids come from LDS (step 0 read them with the relation ids), so
+        //    the rows' loads are not behind a dependent id load
+        auto build_row = [&](int r, Query<FN, CH, V, G>& q, int64_t& ri, bool& rok) {
+            const int64_t qi = qid[r];
+            ri = rrow[r];  // the raw relation id until put() replaces it with the checked one
+            bool qok = qi >= 0 && qi < p.q_rows;
+            rok = ri >= 0 && ri < p.r_rows;
+            q.build(p.qent + (qok ? qi : 0) * p.q_ld, qok, p.rel + (rok ? ri : 0) * p.r_ld + p.r_off, rok, p.D, lane, p);
+        };
+        auto put = [&](int r, const Query<FN, CH, V, G>& q, int64_t ri, bool rok) {
+            vecf<V>* qr = qimg + (size_t)r * NQ * W;
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                qr[lane + k * kWave] = q.q0[k];
+                if constexpr (NQ > 1) qr[W + lane + k * kWave] = q.q1[k];
+            }
+            if (lane == 0) rrow[r] = rok ? ri : -1;
+        };
+        if constexpr (2 * NWV <= kTileMaxRows) {
+            for (int r = w; r < nr; r += 2 * NWV) {
+                const int r2 = r + NWV < nr ? r + NWV : r;
+                Query<FN, CH, V, G> qa, qb;
+                int64_t ri, ri2;
+                bool rok, rok2;
+                build_row(r, qa, ri, rok);
+                build_row(r2, qb, ri2, rok2);
+                put(r, qa, ri, rok);
+                if (r2 != r) put(r2, qb, ri2, rok2);
+            }
+        } else {
+            for (int r = w; r < nr; r += NWV) {
+                Query<FN, CH, V, G> q;
+                int64_t ri;
+                bool rok;
+                build_row(r, q, ri, rok);
+                put(r, q, ri, rok);
+            }
+        }
+        for (int i = t; i < kTileBuckets; i += NT) hist[i] = 0;
         __syncthreads();
+        if (p.tile_dry == 2) return;
+        if constexpr (FN == KGE_INTERHT) {
+            // relation slots: one per run of equal relations among the block's rows (first QS runs; the rows of
+            // later runs read their relation third from the table per candidate)
+            static_assert(kTileMaxRows <= kWave, "one lane per row");
+            if (w == 0) {  // lane r: row r opens a run when its relation differs from row r - 1's
+                const bool in = lane < nr;
+                const int64_t cur = in ? rrow[lane] : 0;
+                const bool open = in && (lane == 0 || cur != rrow[lane - 1]);
+                const uint64_t m = __ballot(open);
+                if (in) {
+                    const int sl = __popcll(m & (lane == 63 ? ~0ull : (2ull << lane) - 1)) - 1;
+                    q2slot[lane] = sl < QS ? sl : -1;
+                }
+            }
+        }
+        int wrk[TPI];  // the item's rank in its bucket, from the counting atomic (no second atomic in the scatter)
+        if (in_regs) {
 #pragma unroll
-        for (int u = 0; u < MU; ++u) {
-            wr[u] = 0;
-            if (u * NT >= p.B) continue;  // block-uniform
-            uint64_t todo = __ballot(bk[u] < NB);
-            while (todo) {  // wave-uniform: one round per distinct bucket of the wave
-                const int v = __builtin_amdgcn_readlane(bk[u], __builtin_ctzll(todo));
-                const uint64_t m = __ballot(bk[u] == v);
-                if (bk[u] == v) wr[u] = lanes_below(m);
-                if (lane == 0) wc[(u * NWV + w) * NB + v] = __popcll(m);
-                todo &= ~m;
+            for (int u = 0; u < TPI; ++u)
+                if (wbk[u] >= 0) wrk[u] = atomicAdd(&hist[wbk[u]], 1);
+        } else {
+            for (int64_t f = t; f < nf; f += NT) {
+                int bk, code;
+                if (item(f, bk, code)) atomicAdd(&hist[bk], 1);
             }
         }
         __syncthreads();
-        if (w == 0) {  // bucket v = lane: prefix over the waves in row order, then over the buckets
-            // (the counts are loaded all together and summed in registers: a dependent LDS round trip per wave
-            // slot cost ~1.5 us of the block's setup)
-            int y[MU * NWV];
+        if (p.tile_dry == 3) return;
+        if constexpr (FN == KGE_INTERHT) {
+            for (int r = w; r < nr; r += NWV) {
+                const int sl = q2slot[r];
+                if (sl < 0 || (r > 0 && q2slot[r - 1] == sl)) continue;  // wave-uniform: the run's first row fills
+                const int64_t ri = rrow[r];
+                const rsrc_t sr = make_rsrc(p.rel + (ri >= 0 ? ri : 0) * p.r_ld + p.r_off, ri >= 0 ? (uint32_t)p.D * 4u : 0u);
 #pragma unroll
-            for (int c = 0; c < MU * NWV; ++c) y[c] = wc[c * NB + lane];
-            int run = 0;
-#pragma unroll
-            for (int c = 0; c < MU * NWV; ++c) {
-                const int v = y[c];
-                y[c] = run;
-                run += v;
+                for (int k = 0; k < G; ++k) q2img[(size_t)sl * W + lane + k * kWave] = bload<V>(sr, goff<V>(lane, k));
             }
-            int incl = run;
+        }
+        if (w == 0) {  // exclusive scan of the bucket counts (4 per lane)
+            constexpr int PL = kTileBuckets / kWave;
+            int v[PL], s = 0;
+#pragma unroll
+            for (int i = 0; i < PL; ++i) {
+                v[i] = hist[lane * PL + i];
+                s += v[i];
+            }
+            int incl = s;
 #pragma unroll
             for (int o = 1; o < kWave; o <<= 1) {
-                const int v = __shfl_up(incl, o, kWave);
-                if (lane >= o) incl += v;
+                const int y = __shfl_up(incl, o, kWave);
+                if (lane >= o) incl += y;
             }
-            const int base = incl - run;
+            int run = incl - s;
 #pragma unroll
-            for (int c = 0; c < MU * NWV; ++c) wc[c * NB + lane] = y[c] + base;
+            for (int i = 0; i < PL; ++i) {
+                hist[lane * PL + i] = run;
+                run += v[i];
+            }
+            if (lane == kWave - 1) cntp[0] = incl;
         }
         __syncthreads();
+        if (in_regs) {
 #pragma unroll
-        for (int u = 0; u < MU; ++u) {
-            if (bk[u] >= NB) continue;
-            const int64_t rank = wc[(u * NWV + w) * NB + bk[u]] + wr[u];
-            if (rank >= g0 && rank < g0 + nr) {
-                brow[rank - g0] = u * NT + t;
-                qid[rank - g0] = qv[u];
-                rrow[rank - g0] = rv[u];
+            for (int u = 0; u < TPI; ++u)
+                if (wbk[u] >= 0) list[hist[wbk[u]] + wrk[u]] = wcd[u];
+        } else {
+            for (int64_t f = t; f < nf; f += NT) {
+                int bk, code;
+                if (item(f, bk, code)) list[atomicAdd(&hist[bk], 1)] = code;
             }
         }
-    } else if (t < nr) {
-        const int64_t b = g0 + t;
-        brow[t] = b;
-        qid[t] = p.q_idx ? p.q_idx[b * p.q_stride] : b;
-        rrow[t] = p.r_idx ? p.r_idx[b * p.r_stride] : b;
-    }
-    __syncthreads();
-    if (p.tile_dry == 1) return;  // A/B knob KGE_TILE_DRY=<level>: the setup up to this point alone
-
-    // 2. counting sort of the block's items of slice x by entity bucket
-    const int64_t nf = (int64_t)nr * Np;
-    // no 64-bit divisions in the walk (an emulated int64 divide is ~100 instructions): the item's row by a
-    // float reciprocal corrected to the exact quotient (f < R (N + 1) < 2^21), the entity bucket by a float
-    // scale (any monotone map of the slice onto the buckets orders the sweep)
-    const int Np32 = (int)Np;
-    const float inv_np = 1.f / (float)Np32, bscale = (float)kTileBuckets / (float)S;
-    auto item = [&](int64_t f64, int& bucket, int& code) -> bool {
-        const int f = (int)f64;
-        int r = (int)((float)f * inv_np);
-        if (r * Np32 > f) --r;
-        if ((r + 1) * Np32 <= f) ++r;
-        const int n = f - r * Np32;
-        const int64_t b = brow[r];
-        const int64_t id = n < p.N ? p.c_idx[b * p.c_stride + n] : p.pos_base[b * 3 + 2];
-        const int64_t row = id - p.c_base;
-        const bool valid = row >= 0 && row < p.c_rows;
-        if (valid ? (row < e_lo || row >= e_hi) : x != 0) return false;
-        bucket = valid ? min(kTileBuckets - 1, (int)((float)(int)(row - e_lo) * bscale)) : 0;
-        code = (r << 16) | n;
-        return true;
-    };
-    // the ids are loaded once, all in flight together, when the block's walk fits TPI per thread (C2: 4 112
-    // items over 768 threads); otherwise the walk is made twice (count, then scatter)
-    // 17 at 16 waves: a 16-row block's 16 x 1 025 tail-batch items at N = 1 024 (C4) over 1 024 threads, walked
-    // once (C4 tail-batch 94.5 -> 88 us); 16 at fewer waves, where the 17th slot measured ~1 us slower at C3
-    constexpr int TPI = NWV >= 16 ? 17 : 16;
-    int wbk[TPI], wcd[TPI];
-    const bool in_regs = !pl && nf <= (int64_t)TPI * NT;  // block-uniform
-    // (their loads are issued here, before the query build, so both latencies overlap)
-    if (in_regs) {
-#pragma unroll
-        for (int u = 0; u < TPI; ++u) {
-            const int64_t f = (int64_t)u * NT + t;
-            wbk[u] = -1;
-            if (f < nf && !item(f, wbk[u], wcd[u])) wbk[u] = -1;
-        }
-    }
-
-    // 1. the rows' query operands; with fewer waves than rows, two rows per wave built side by side (branch-free:
-    //    both rows' loads in flight together). The ids come from LDS (step 0 read them with the relation ids), so
-    //    the rows' loads are not behind a dependent id load
-    auto build_row = [&](int r, Query<FN, CH, V, G>& q, int64_t& ri, bool& rok) {
-        const int64_t qi = qid[r];
-        ri = rrow[r];  // the raw relation id until put() replaces it with the checked one
-        bool qok = qi >= 0 && qi < p.q_rows;
-        rok = ri >= 0 && ri < p.r_rows;
-        q.build(p.qent + (qok ? qi : 0) * p.q_ld, qok, p.rel + (rok ? ri : 0) * p.r_ld + p.r_off, rok, p.D, lane, p);
-    };
-    auto put = [&](int r, const Query<FN, CH, V, G>& q, int64_t ri, bool rok) {
-        vecf<V>* qr = qimg + (size_t)r * NQ * W;
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-            qr[lane + k * kWave] = q.q0[k];
-            if constexpr (NQ > 1) qr[W + lane + k * kWave] = q.q1[k];
-        }
-        if (lane == 0) rrow[r] = rok ? ri : -1;
-    };
-    if constexpr (2 * NWV <= kTileMaxRows) {
-        for (int r = w; r < nr; r += 2 * NWV) {
-            const int r2 = r + NWV < nr ? r + NWV : r;
-            Query<FN, CH, V, G> qa, qb;
-            int64_t ri, ri2;
-            bool rok, rok2;
-            build_row(r, qa, ri, rok);
-            build_row(r2, qb, ri2, rok2);
-            put(r, qa, ri, rok);
-            if (r2 != r) put(r2, qb, ri2, rok2);
-        }
-    } else {
-        for (int r = w; r < nr; r += NWV) {
-            Query<FN, CH, V, G> q;
-            int64_t ri;
-            bool rok;
-            build_row(r, q, ri, rok);
-            put(r, q, ri, rok);
-        }
-    }
-    for (int i = t; i < kTileBuckets; i += NT) hist[i] = 0;
-    __syncthreads();
-    if (p.tile_dry == 2) return;
-    if constexpr (FN == KGE_INTERHT) {
-        // relation slots: one per run of equal relations among the block's rows (first QS runs; the rows of
-        // later runs read their relation third from the table per candidate)
-        static_assert(kTileMaxRows <= kWave, "one lane per row");
-        if (w == 0) {  // lane r: row r opens a run when its relation differs from row r - 1's
-            const bool in = lane < nr;
-            const int64_t cur = in ? rrow[lane] : 0;
-            const bool open = in && (lane == 0 || cur != rrow[lane - 1]);
-            const uint64_t m = __ballot(open);
-            if (in) {
-                const int sl = __popcll(m & (lane == 63 ? ~0ull : (2ull << lane) - 1)) - 1;
-                q2slot[lane] = sl < QS ? sl : -1;
-            }
-        }
-    }
-    int wrk[TPI];  // the item's rank in its bucket, from the counting atomic (no second atomic in the scatter)
-    if (pl) {
-    } else if (in_regs) {
-#pragma unroll
-        for (int u = 0; u < TPI; ++u)
-            if (wbk[u] >= 0) wrk[u] = atomicAdd(&hist[wbk[u]], 1);
-    } else {
-        for (int64_t f = t; f < nf; f += NT) {
-            int bk, code;
-            if (item(f, bk, code)) atomicAdd(&hist[bk], 1);
-        }
-    }
-    __syncthreads();
-    if (p.tile_dry == 3) return;
-    if constexpr (FN == KGE_INTERHT) {
-        for (int r = w; r < nr; r += NWV) {
-            const int sl = q2slot[r];
-            if (sl < 0 || (r > 0 && q2slot[r - 1] == sl)) continue;  // wave-uniform: the run's first row fills
-            const int64_t ri = rrow[r];
-            const rsrc_t sr = make_rsrc(p.rel + (ri >= 0 ? ri : 0) * p.r_ld + p.r_off, ri >= 0 ? (uint32_t)p.D * 4u : 0u);
-#pragma unroll
-            for (int k = 0; k < G; ++k) q2img[(size_t)sl * W + lane + k * kWave] = bload<V>(sr, goff<V>(lane, k));
-        }
-    }
-    if (!pl && w == 0) {  // exclusive scan of the bucket counts (4 per lane)
-        constexpr int PL = kTileBuckets / kWave;
-        int v[PL], s = 0;
-#pragma unroll
-        for (int i = 0; i < PL; ++i) {
-            v[i] = hist[lane * PL + i];
-            s += v[i];
-        }
-        int incl = s;
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const int y = __shfl_up(incl, o, kWave);
-            if (lane >= o) incl += y;
-        }
-        int run = incl - s;
-#pragma unroll
-        for (int i = 0; i < PL; ++i) {
-            hist[lane * PL + i] = run;
-            run += v[i];
-        }
-        if (lane == kWave - 1) cntp[0] = incl;
-    }
-    __syncthreads();
-    if (pl) {
-    } else if (in_regs) {
-#pragma unroll
-        for (int u = 0; u < TPI; ++u)
-            if (wbk[u] >= 0) list[hist[wbk[u]] + wrk[u]] = wcd[u];
-    } else {
-        for (int64_t f = t; f < nf; f += NT) {
-            int bk, code;
-            if (item(f, bk, code)) list[atomicAdd(&hist[bk], 1)] = code;
-        }
-    }
-    __syncthreads();
-    const int cnt = pl ? pcnt : cntp[0];
+        __syncthreads();
+        cnt = cntp[0];
+    }  // !PLANNED
 
     if (p.tile_dry) return;
     // 3. the sweep: wave w takes items w, w + NWV, w + 2 NWV, ...; with DEPTH 2 the next item's
@@ -1483,7 +1591,8 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
     // the progress board of a planned step (kge_internal.h: kSweepBoardInts) as a buffer over this slice's line
     // (range-checked by the hardware: a store past the line is dropped). Lane l < 32 reads row group l's entry;
     // bv is the line as loaded with the item before (no dependent round trip); thread 0 publishes
-    const bool has_board = pl && p.tile_board && (p.tile_blocks >> 3) <= kSweepBoardLine;
+    // (BOARD: launch_tile chooses the instance from p.tile_board && row groups <= kSweepBoardLine)
+    constexpr bool has_board = BOARD;
     const rsrc_t brs = make_rsrc(has_board ? p.tile_board + x * kSweepBoardLine : nullptr, has_board ? kSweepBoardLine * 4u : 0u);
     const uint32_t boff_ld = (uint32_t)(lane & (kSweepBoardLine - 1)) * 4u;
     const uint32_t boff_st = t == 0 ? (uint32_t)gi * 4u : kSweepBoardLine * 4u;  // past the line: dropped
@@ -1491,13 +1600,16 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
     const bool bpeer = has_board && lane < (p.tile_blocks >> 3) && lane != gi;  // another existing row group
     int bv = 0;
 #ifdef KGE_PROFILING_KNOBS
-    // clock marks of the block (wave 0): sweep start, past entity buckets 64 / 128 / 192 (mirrored under a
-    // descending sweep), sweep end; then the XCC id
-    long long* const clk = (pl && p.tile_clk && w == 0) ? p.tile_clk + ((int64_t)x * (p.tile_blocks >> 3) + gi) * kSweepClkMarks : nullptr;
+    // clock marks of the block (kge_internal.h: the clock record). Wave 0: sweep start, past entity buckets 64 /
+    // 128 / 192 (mirrored under a descending sweep), sweep end, the XCC id, block entry; every wave: its sweep's end
+    // and its exit. Plain stores by lane 0
+    long long* const bclk = (PLANNED && p.tile_clk) ? p.tile_clk + ((int64_t)x * (p.tile_blocks >> 3) + gi) * kSweepClkMarks : nullptr;
+    long long* const clk = w == 0 ? bclk : nullptr;
     int cmark = 0;
     if (clk && lane == 0) {
         clk[0] = wall_clock64();
         clk[5] = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15;  // HW_REG_XCC_ID, bits 3:0
+        clk[6] = clk_entry;
     }
 #endif
     for (int c0 = w; c0 < cnt; c0 += NT) {
@@ -1507,10 +1619,15 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
         if (lane < nc) {
             // p.tile_rev: the list walked from its end (descending entity order), the same items
             const int ci = p.tile_rev ? cnt - 1 - (c0 + NWV * lane) : c0 + NWV * lane;
-            if (pl) {  // (checked entity id, code): no dependent id load
-                const int2 e = plist[plo + ci];
-                code = e.y;
-                my_id = e.x;
+            if constexpr (PLANNED) {  // (checked entity id, code): no dependent id load; the first from the prologue
+                if (c0 == w) {  // wave-uniform
+                    code = pre_code;
+                    my_id = pre_id;
+                } else {
+                    const auto e = __builtin_amdgcn_raw_buffer_load_b64(prs, (uint32_t)ci * 8u, 0, 0);
+                    code = (int)e[1];
+                    my_id = (int)e[0];
+                }
             } else {
                 code = list[ci];
                 const int r = code >> 16, n = code & 0xFFFF;
@@ -1558,7 +1675,7 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
         // an item's loads, behind the lead throttle: at most one fixed nap per item, whatever the board holds
         auto fetch = [&](Item& it, int j) {
             const int own = __builtin_amdgcn_readlane(my_prog, j);
-            if (has_board) {  // block-uniform: without a board the sweep issues none of this (at C4's 2 KB rows
+            if constexpr (has_board) {  // without a board the sweep issues none of this (at C4's 2 KB rows
                 // the board's instructions alone, on a 0-byte buffer, cost 7.7 %: profiles/r07_bench_ab_first.txt)
                 const bool led = bpeer && (bv & ~kSweepDone) == btag && (bv & kSweepDone) + p.tile_lead < own;
                 if (__ballot(led)) __builtin_amdgcn_s_sleep(kSweepNap);
@@ -1610,13 +1727,14 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
             }
         }
     }
-    if (has_board) {  // nobody naps for a block whose sweep has ended
+    if constexpr (has_board) {  // nobody naps for a block whose sweep has ended
         vecf<1> pub;
         pub.a[0] = __int_as_float(btag | kSweepDone);
         bstore<1>(brs, boff_st, pub);
     }
 #ifdef KGE_PROFILING_KNOBS
     if (clk && lane == 0) clk[4] = wall_clock64();
+    if (bclk && lane == 0) bclk[kSweepClkWave + 2 * w] = wall_clock64();
 #endif
     if constexpr (CH) {
         if (!p.tile_pos) return;
@@ -1624,12 +1742,12 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
         // (model.py:127-146), one wave per row
         for (int r = w; r < nr; r += NWV) {
             const int64_t b = brow[r];
-            const int4 pm = pl ? pmeta[r] : make_int4(0, 0, 0, 0);
-            const int64_t tt = pl ? pm.w : p.pos_base[b * 3 + 2], row = tt - p.c_base;
+            const int4 pm = PLANNED ? pmeta[r] : make_int4(0, 0, 0, 0);
+            const int64_t tt = PLANNED ? pm.w : p.pos_base[b * 3 + 2], row = tt - p.c_base;
             const bool valid = row >= 0 && row < p.c_rows;
             if (valid ? (row < e_lo || row >= e_hi) : x != 0) continue;  // wave-uniform
             Query<FN, false, V, G> qp;
-            const int64_t hi = pl ? pm.y : p.pos_base[b * 3], rj = pl ? pm.z : p.pos_base[b * 3 + 1];
+            const int64_t hi = PLANNED ? pm.y : p.pos_base[b * 3], rj = PLANNED ? pm.z : p.pos_base[b * 3 + 1];
             const bool hok = hi >= 0 && hi < p.q_rows, rjok = rj >= 0 && rj < p.r_rows;
             qp.build(p.qent + (hok ? hi : 0) * p.q_ld, hok, p.rel + (rjok ? rj : 0) * p.r_ld + p.r_off, rjok, p.D,
                      lane, p);
@@ -1643,6 +1761,9 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
             }
         }
     }
+#ifdef KGE_PROFILING_KNOBS
+    if (bclk && lane == 0) bclk[kSweepClkWave + 2 * w + 1] = wall_clock64();  // (a planned step scores positives)
+#endif
 }
 
 // Scoring in the XCD-sliced order (kge_score_indexed / kge_score_sharded, N >= 128): the table's rows
@@ -3788,15 +3909,28 @@ namespace kge_impl {
 // ---------------------------------------------------------------------------------------------
 // dispatch over (kind, candidate side, vector width, groups per lane) for one score function
 // ---------------------------------------------------------------------------------------------
-template <int FN, bool CH, int V, int G, int NWV, int DEPTH = 2>
-void launch_tile(const ScoreParams& p, hipStream_t st, int blocks) {
+template <int FN, bool CH, int V, int G, int NWV, int DEPTH, bool PLANNED, bool BOARD>
+void launch_tile_as(const ScoreParams& p, hipStream_t st, int blocks) {
     // up to the whole 160 KB of a CU's LDS per block (set once per instantiation)
     static const bool lds_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH, PLANNED, BOARD>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kTileLdsMax) == hipSuccess;
     (void)lds_ok;
-    hipLaunchKernelGGL((step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH>), dim3(blocks), dim3(NWV * kWave), p.tile_lds, st,
-                       p);
+    hipLaunchKernelGGL((step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH, PLANNED, BOARD>), dim3(blocks),
+                       dim3(NWV * kWave), p.tile_lds, st, p);
+}
+
+// The instance of a tile launch: a planned step (p.tile_plan) runs the planned prologue, with the lead throttle's
+// code only where a board reaches the kernel; an unplanned step sweeps two candidate rows deep (tile_plan).
+template <int FN, bool CH, int V, int G, int NWV, int DEPTH = 2>
+void launch_tile(const ScoreParams& p, hipStream_t st, int blocks) {
+    if (!p.tile_plan) {
+        if constexpr (DEPTH == 2) launch_tile_as<FN, CH, V, G, NWV, 2, false, false>(p, st, blocks);
+    } else if (p.tile_board && (p.tile_blocks >> 3) <= kSweepBoardLine) {
+        launch_tile_as<FN, CH, V, G, NWV, DEPTH, true, true>(p, st, blocks);
+    } else {
+        launch_tile_as<FN, CH, V, G, NWV, DEPTH, true, false>(p, st, blocks);
+    }
 }
 
 // Launches kind `kind`; false when it has no (FN, CH, V, G) instantiation (nothing was launched). The guards are
@@ -3844,7 +3978,8 @@ bool launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
         static_assert(kind_has(KIND_STEP_FWD_TILE, FN, CH, G) == kind_has(KIND_SCORE_TILE, FN, CH, G), "one kernel");
         if constexpr (kind_has(KIND_STEP_FWD_TILE, FN, CH, G)) {
             // (waves, candidate rows in flight per wave): 8 x 2, 12 x 2, 12 x 1, 16 x 2, 16 x 1
-            const bool d1 = p.tile_depth == 1;
+            // (one row in flight is a planned step's choice: kge_step_planner_set_form)
+            const bool d1 = p.tile_plan && p.tile_depth == 1;
             if (p.tile_waves == 16)
                 d1 ? launch_tile<FN, CH, V, G, 16, 1>(p, st, blocks) : launch_tile<FN, CH, V, G, 16>(p, st, blocks);
             else if (p.tile_waves == 12)

@@ -140,7 +140,15 @@ constexpr int kSweepTagShift = 9;                     // progress: 0 .. kTileBuc
 constexpr int kSweepDone = (1 << kSweepTagShift) - 1;
 constexpr int kSweepTagMask = (1 << (31 - kSweepTagShift)) - 1;
 constexpr int kSweepNap = 8;  // s_sleep units of 64 clocks: ~0.2 us, about a tenth of a wave's time per item at C2
-constexpr int kSweepClkMarks = 6;  // per block: sweep start, wave 0 past buckets 64 / 128 / 192, sweep end, XCC id
+// The clock record of a planned step (kge_step_planner_set_clocks, profiling builds), int64 words of the 100 MHz
+// clock: per scoring block (slice x, row group g: record x * groups + g) kSweepClkMarks words: [0] wave 0's sweep
+// start, [1..3] wave 0 past buckets 64 / 128 / 192, [4] wave 0's sweep end, [5] the XCC id, [6] block entry,
+// [7] unused, then per wave w at [kSweepClkWave + 2 w] its sweep's end and at [.. + 1] its exit (after the
+// head-batch positives; 0 for waves the block does not have). After the 8 * groups scoring records, per plan block
+// of the launch's tail two words: entry, thread 0's exit. kge_sweep_clk_words: the whole record.
+constexpr int kSweepClkWave = 8;
+constexpr int kSweepClkMarks = kSweepClkWave + 2 * 16;
+constexpr int64_t kge_sweep_clk_words(int64_t groups) { return groups * 8 * kSweepClkMarks + groups * 2; }
 
 // ---------------------------------------------------------------------------------------------
 // The tile scorer's step plan (kge_step_plan / kge_step_forward_planned): everything step_fwd_tile_kernel

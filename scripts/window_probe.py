@@ -4,7 +4,8 @@
 16 x 2 sweep without a board, selected through the planner's setters in one process; (3) `tune`: leads between 8
 and 24 and the board's own cost. Device us per step, events around 300 steps after 50 warmup, rounds
 interleaved, same batches as bench.py; outputs compared bitwise.
-Usage: python scripts/window_probe.py skew [wl..] | forms [wl..] | tune [wl..]"""
+(4) `timeline` (the same profiling library): where a planned step's launch spends its time outside the sweep.
+Usage: python scripts/window_probe.py skew [wl..] | timeline [wl..] | forms [wl..] | tune [wl..]"""
 import json
 import os
 import statistics
@@ -21,6 +22,20 @@ from customknowledgegraphembedding_amd._lib import FN_IDS, check  # noqa: E402
 bench.ops = ops  # bench.py binds its module-level `ops` only inside main(); StepRunner needs it (as sweep_probe.py)
 dev = torch.device("cuda", 0)
 ROUNDS = 6  # round 1 is dropped
+# the clock record (csrc/kge_internal.h): per scoring block CLK_MARKS int64 words (the per-wave pairs from CLK_WAVE
+# on), then two per plan block
+CLK_WAVE = 8
+CLK_MARKS = CLK_WAVE + 2 * 16
+
+
+def set_clocks(p, B):
+    """Hands the planner a zeroed clock record; returns (row groups, the record)."""
+    groups = (B + 15) // 16  # 16 rows per group; the library refuses a buffer smaller than its own count
+    clk = torch.zeros(groups * (8 * CLK_MARKS + 2), dtype=torch.int64, device=dev)
+    assert p._lib.kge_step_planner_set_clocks(p._h, clk.data_ptr(), clk.numel() * 8 - 8) != 0, \
+        "the tile plan has fewer than 16 rows per group for this shape: size the clock buffer from its groups"
+    check(p._lib.kge_step_planner_set_clocks(p._h, clk.data_ptr(), clk.numel() * 8), "kge_step_planner_set_clocks")
+    return groups, clk
 
 
 def timed(f, n=300, warm=50):
@@ -52,11 +67,7 @@ def skew(wl):
     for waves, depth, lead in ((12, 2, 0), (12, 1, 0), (16, 1, 0), (12, 2, 16), (16, 2, 0)):
         r = runner(m, batches, fn, waves, depth, lead)
         p = r.planner
-        groups = (w["B"] + 15) // 16  # 16 rows per group; the library refuses a buffer smaller than its own count
-        clk = torch.zeros(8 * groups * 6, dtype=torch.int64, device=dev)
-        assert p._lib.kge_step_planner_set_clocks(p._h, clk.data_ptr(), clk.numel() * 8 - 8) != 0, \
-            "the tile plan has fewer than 16 rows per group for this shape: size the clock buffer from its groups"
-        check(p._lib.kge_step_planner_set_clocks(p._h, clk.data_ptr(), clk.numel() * 8), "kge_step_planner_set_clocks")
+        groups, clk = set_clocks(p, w["B"])
         for i in range(40):
             r(i)
         spreads, durs, one_xcc = [], [], True
@@ -64,7 +75,7 @@ def skew(wl):
             clk.zero_()
             r(i)
             torch.cuda.synchronize()
-            c = clk.view(8, groups, 6).cpu()
+            c = clk[:8 * groups * CLK_MARKS].view(8, groups, CLK_MARKS)[:, :, :6].cpu()
             t = c[:, :, :5].double() / 100.0  # 100 MHz ticks -> us
             seen = (c[:, :, :5] > 0).all(1)
             sp = t.max(1).values - t.min(1).values  # [slice, mark]
@@ -83,6 +94,56 @@ def skew(wl):
                                "max": round(float(d.max()), 2),
                                "rel_sigma_within_slice": round(float((d.std(2) / d.mean(2)).median()), 4)},
             "slice_blocks_share_one_xcc": one_xcc}), flush=True)
+
+
+def timeline(wl):
+    """The planned step's launch as a timeline, in the library's own sweep form: per mark, the median and the worst
+    (latest) block, in us after the step's earliest block entry, over six sampled steps of both modes; the plan
+    (tail) blocks' earliest and latest entry and exit; the latest exit of any block."""
+    w = bench.WORKLOADS[wl]
+    m, batches = bench.make_inputs(w, 0, dev)
+    r = bench.StepRunner(m, batches, FN_IDS[w["fn"]], planned=True)
+    groups, clk = set_clocks(r.planner, w["B"])
+    nsc = 8 * groups
+    for i in range(40):
+        r(i)
+    marks = {k: [] for k in ("sweep_start", "wave0_sweep_end", "last_wave_sweep_end", "block_exit")}
+    plan_in, plan_out, last = [], [], []
+    for i in range(40, 46):
+        clk.zero_()
+        r(i)
+        torch.cuda.synchronize()
+        c = clk.cpu().double() / 100.0  # 100 MHz ticks -> us
+        blk = c[:nsc * CLK_MARKS].view(nsc, CLK_MARKS)
+        per_wave = blk[:, CLK_WAVE:].view(nsc, 16, 2)
+        t0 = float(blk[:, 6].min())
+        assert t0 > 0, "no clock marks: the library is not a -DKGE_PROFILING_KNOBS build of this source"
+        marks["sweep_start"].append(blk[:, 0] - t0)
+        marks["wave0_sweep_end"].append(blk[:, 4] - t0)
+        marks["last_wave_sweep_end"].append(per_wave[:, :, 0].max(1).values - t0)
+        marks["block_exit"].append(per_wave[:, :, 1].max(1).values - t0)
+        entry = blk[:, 6] - t0
+        pb = c[nsc * CLK_MARKS:nsc * CLK_MARKS + 2 * groups].view(groups, 2)
+        pb = pb[pb[:, 0] > 0] - t0  # (the last sampled step plans a batch like every other)
+        if len(pb):
+            plan_in.append(pb[:, 0])
+            plan_out.append(pb[:, 1])
+        last.append(max(float(marks["block_exit"][-1].max()), float(pb[:, 1].max()) if len(pb) else 0.0))
+        marks.setdefault("block_entry", []).append(entry)
+
+    def mw(v):
+        s = torch.stack(v)  # [step, block]
+        return {"median": round(float(s.median()), 2), "worst": round(float(s.max()), 2),
+                "worst_median_over_steps": round(float(s.max(1).values.median()), 2)}
+    out = {"workload": w["name"], "form": r.planner.form(), "us_after_earliest_block_entry": {k: mw(v) for k, v in marks.items()}}
+    if plan_in:
+        pi, po = torch.cat(plan_in), torch.cat(plan_out)
+        out["plan_blocks"] = {"entry_earliest": round(float(pi.min()), 2), "entry_latest": round(float(pi.max()), 2),
+                              "exit_earliest": round(float(po.min()), 2), "exit_latest": round(float(po.max()), 2)}
+    out["latest_exit_of_any_block"] = {"median_over_steps": round(statistics.median(last), 2), "max": round(max(last), 2)}
+    print(json.dumps(out), flush=True)
+    del m, batches
+    torch.cuda.empty_cache()
 
 
 def forms(wl, tune=False):
@@ -126,8 +187,10 @@ def forms(wl, tune=False):
 
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "forms"
-    for wl in (sys.argv[2:] or (["c2", "c3", "c4"] if what == "forms" else ["c2"])):
+    for wl in (sys.argv[2:] or (["c2", "c3", "c4"] if what in ("forms", "timeline") else ["c2"])):
         if what == "skew":
             skew(wl)
+        elif what == "timeline":
+            timeline(wl)
         else:
             forms(wl, tune=what == "tune")
