@@ -493,13 +493,16 @@ struct StepGrads {
     const float* cand_stats;
 };
 
-// widest vector width every operand allows, then the groups-per-lane bucket
+// widest vector width every operand allows, then the groups-per-lane bucket. The sharded train step's positive
+// query rows (qent_pos, q_ld) and query-gradient buffer (sh_dq, rows of nq D floats) are read and written with
+// the same width, so they count when set.
 int pick_vg(const ScoreParams& p, int& V, int& G) {
     const int cand[3] = {4, 2, 1};
     V = 1;
     for (int v : cand) {
         if (p.D % v == 0 && p.q_ld % v == 0 && p.r_ld % v == 0 && p.r_off % v == 0 && p.c_ld % v == 0 &&
-            aligned(p.qent, 4 * v) && aligned(p.rel, 4 * v) && aligned(p.cent, 4 * v)) {
+            aligned(p.qent, 4 * v) && aligned(p.rel, 4 * v) && aligned(p.cent, 4 * v) &&
+            aligned(p.qent_pos, 4 * v) && aligned(p.sh_dq, 4 * v)) {
             V = v;
             break;
         }
@@ -552,7 +555,10 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
     if (rc) return rc;
     if (p.B < 0 || p.N < 0 || p.D <= 0) return fail(KGE_EINVAL, "bad shape (B, N, D)");
     if (p.B == 0 || p.N == 0) return ok();
-    if (!p.qent || !p.rel || !p.cent) return fail(KGE_EINVAL, "null table pointer");
+    // a rank of the sharded train step that owns no rows has no shard to point at: nothing reads p.cent then
+    const bool no_rows =
+        p.c_rows == 0 && (kind == KIND_SHARD_FWD_GRAD || kind == KIND_SHARD_POS || kind == KIND_SHARD_EPILOGUE);
+    if (!p.qent || !p.rel || (!p.cent && !no_rows)) return fail(KGE_EINVAL, "null table pointer");
     int V = 1, G = 1;
     rc = pick_vg(p, V, G);
     if (rc) return rc;
@@ -620,7 +626,7 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
     if (blocks > INT32_MAX) return fail(KGE_EINVAL, "problem too large for one launch");
     const bool ch = k.ch && mode == KGE_HEAD_BATCH;
     if (k.no_protate && (G > k.max_g || fn == KGE_PROTATE))
-        return fail(KGE_ENOTSUP, "the fused forward + query gradient needs D <= 1024 and no pRotatE");
+        return fail(KGE_ENOTSUP, "the fused forward + query gradient needs D / V <= 256 and no pRotatE");
     if (G > k.max_g) return fail(KGE_ENOTSUP, "dimension too large");
     if (k.g_whole_waves && G % kWavesPerBlock) return fail(KGE_ENOTSUP, "the streaming backward needs G % 4 == 0");
     // a (kind, function, side, V, G) without an instantiation launches nothing and says so
@@ -1856,8 +1862,11 @@ static int step_backward_impl(const Tables& t, const Batch& b, const StepGrads& 
     if (rc) return rc;
     if (mode == KGE_SINGLE) return fail(KGE_EINVAL, "kge_step_backward needs a negative mode (0 or 1)");
     if (B < 0 || N <= 0 || t.D <= 0 || t.nentity < 0 || t.nrelation < 0) return fail(KGE_EINVAL, "bad shape");
-    if (!t.ent || !t.rel || !b.pos || !b.neg || !g.neg_scores || !g.pos_scores || !g.d_out_neg || !g.d_out_pos ||
-        !g.d_rel || (!adam && !g.d_ent) || (adam && (!m_ent || !v_ent)))
+    // the sharded train step's backward on a rank without rows (o.epilogue_done, nentity 0) has no table and no
+    // moments: phase 2 is skipped below
+    const bool no_rows = o.epilogue_done && t.nentity == 0;
+    if ((!t.ent && !no_rows) || !t.rel || !b.pos || !b.neg || !g.neg_scores || !g.pos_scores || !g.d_out_neg ||
+        !g.d_out_pos || !g.d_rel || (!adam && !g.d_ent) || (adam && !no_rows && (!m_ent || !v_ent)))
         return fail(KGE_EINVAL, "null pointer");
     if (B * N + 3 * B >= (int64_t)INT32_MAX || t.nentity >= (int64_t)INT32_MAX)
         return fail(KGE_EINVAL, "too many gradient events for 32-bit codes");
@@ -2361,7 +2370,8 @@ static int shard_check(const Tables& t, const Batch& b, const ShardArgs& a, void
     if (b.B <= 0 || b.N <= 0 || t.D <= 0 || t.nentity < 0 || a.world < 1 || a.rank < 0 || a.rank >= a.world ||
         a.home_B <= 0 || a.home_B * a.world != b.B)
         return fail(KGE_EINVAL, "bad shape: need Bg = world * home_B > 0, N, D > 0, 0 <= rank < world");
-    if (!t.ent || !a.qent || !a.qent_pos || !t.rel || !b.pos || !b.neg || !a.weight)
+    // a rank that owns no rows (shard_rows 0: fewer entities than ranks) has no shard to point at
+    if ((!t.ent && t.nentity > 0) || !a.qent || !a.qent_pos || !t.rel || !b.pos || !b.neg || !a.weight)
         return fail(KGE_EINVAL, "null pointer");
     if (b.B * b.N + 3 * b.B >= (int64_t)INT32_MAX || t.nentity >= (int64_t)INT32_MAX)
         return fail(KGE_EINVAL, "too many gradient events for 32-bit codes");
@@ -2398,6 +2408,20 @@ static void shard_params(ScoreParams& p, const Tables& t, const Batch& b, const 
     p.sh_merged = w.merged;
 }
 
+// The kernel instance of a sharded train call (p: shard_params and the call's dq), checked by all three calls
+// before anything is launched or written. The train kinds keep kFwdGradMaxG groups of V floats per lane, so the
+// step exists for D / V <= kFwdGradMaxG * 64: 1024 / 512 / 256 floats per half at vector width 4 / 2 / 1.
+static int shard_instance(const ScoreParams& p) {
+    int V = 1, G = 1;
+    const int rc = pick_vg(p, V, G);  // (its own refusal, past kMaxG groups, is restated with this step's limit)
+    if (rc || G > kFwdGradMaxG)
+        return fail(KGE_ENOTSUP, "the sharded train step needs D / V <= " + std::to_string(kFwdGradMaxG * kWave) +
+                                     " per half (D <= 1024 / 512 / 256 where every row stride, offset and base "
+                                     "address is a multiple of 16 / 8 / 4 bytes): D = " + std::to_string(p.D) +
+                                     " at vector width V = " + std::to_string(V));
+    return 0;
+}
+
 extern "C" {
 
 int kge_shard_nq(int fn) { return valid_fn(fn) ? shard_nq(fn) : 0; }
@@ -2423,14 +2447,16 @@ int kge_shard_train_forward(int fn, int mode, const float* shard, int64_t shard_
     const ShardWs w = shard_ws_layout((char*)workspace, fn, shard_rows, nrelation, rel_ld, Bg, N, D);
     if (workspace_bytes < w.bytes) return fail(KGE_EINVAL, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    // per-call state only: the local rows' event counters are zeroed here
-    if (shard_rows > 0 && hipMemsetAsync(w.step.count, 0, (size_t)align256(shard_rows * 4), st) != hipSuccess)
-        return check_launch("kge_shard_train_forward memset");
     ScoreParams p;
     shard_params(p, t, b, a, w);
     p.ev_count = w.step.count;
     p.sh_stats = stats;
     p.sh_dq = dq;
+    rc = shard_instance(p);
+    if (rc) return rc;
+    // per-call state only: the local rows' event counters are zeroed here
+    if (shard_rows > 0 && hipMemsetAsync(w.step.count, 0, (size_t)align256(shard_rows * 4), st) != hipSuccess)
+        return check_launch("kge_shard_train_forward memset");
     rc = run_score(fn, mode, p, KIND_SHARD_FWD_GRAD, stream);
     if (rc) return rc;
     p.ev_count = nullptr;
@@ -2459,6 +2485,8 @@ int kge_shard_train_combine(int fn, int mode, const float* shard, int64_t shard_
     p.out_neg = out_neg;
     p.out_pos_raw = out_pos_raw;
     p.out_pos_ls = out_pos;
+    rc = shard_instance(p);  // the combine itself has one form; a step the other two calls refuse is refused here too
+    if (rc) return rc;
     const int64_t blocks = (Bg + kWavesPerBlock - 1) / kWavesPerBlock;
     hipLaunchKernelGGL(shard_combine_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, p);
     return check_launch("kge_shard_train_combine");
@@ -2478,19 +2506,22 @@ int kge_shard_train_backward(int fn, int mode, float* shard, int64_t shard_rows,
     int rc = shard_check(t, b, a, workspace, workspace_bytes);
     if (rc) return rc;
     if (step < 1) return fail(KGE_EINVAL, "step is 1-based");
-    if (!dq || !loss || !m_ent || !v_ent || !m_rel || !v_rel) return fail(KGE_EINVAL, "null pointer");
+    if (!dq || !loss || (shard_rows > 0 && (!m_ent || !v_ent)) || !m_rel || !v_rel)
+        return fail(KGE_EINVAL, "null pointer");
     const ShardWs w = shard_ws_layout((char*)workspace, fn, shard_rows, nrelation, rel_ld, Bg, N, D);
     if (workspace_bytes < w.bytes) return fail(KGE_EINVAL, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
+    ScoreParams e;
+    shard_params(e, t, b, a, w);
+    e.sh_dq = const_cast<float*>(dq);
+    rc = shard_instance(e);
+    if (rc) return rc;
     // bucket offsets of the owned rows' events (counted by the forward)
     if (shard_rows > 0)
         hipLaunchKernelGGL(scan_block_kernel, dim3(1), dim3(kScanTile), 0, st, w.step.count, shard_rows, w.step.off,
                            w.step.cursor, 0, (int)(Bg * N + 3 * Bg));
     rc = check_launch("kge_shard_train_backward scan");
     if (rc) return rc;
-    ScoreParams e;
-    shard_params(e, t, b, a, w);
-    e.sh_dq = const_cast<float*>(dq);
     e.qbuf = w.step.qbuf;
     e.qg_ent = w.step.qg_ent;
     e.qg_rel = w.step.qg_rel;

@@ -489,10 +489,14 @@ int launched(const char* what) {
     return set_error(0, "");
 }
 
-int check_world(int64_t Bg, int world, int64_t nentity) {
+// empty_ranks: ranks without rows are allowed (nentity < world). The query exchange of the sharded train step
+// takes them (Owners::of never divides by the zero row count: every id in range is below `split`); the forward's
+// bucket, scoring and finish do not (a bucket's slice height would be 0).
+int check_world(int64_t Bg, int world, int64_t nentity, bool empty_ranks = false) {
     if (world < 1 || world > kMaxWorld) return set_error(KGE_ENOTSUP, "row-sharded exchange: world must be 1..64");
     if (Bg < 0 || Bg % world) return set_error(KGE_EINVAL, "row-sharded exchange: Bg must split evenly over ranks");
-    if (nentity < world) return set_error(KGE_EINVAL, "row-sharded exchange: fewer entities than ranks");
+    if (nentity < (empty_ranks ? 0 : world))
+        return set_error(KGE_EINVAL, "row-sharded exchange: fewer entities than ranks");
     return 0;
 }
 
@@ -519,7 +523,7 @@ extern "C" {
 int kge_shard_plan(const int64_t* pos, const int64_t* neg, int64_t neg_ld, int64_t Bg, int64_t N, int64_t nentity,
                    int world, int chunks, int mode, int flags, int rank, int* cnt, int* hpre, int* qown, int* qslot,
                    int* summary, int* bucket, int* bucket_start, void* stream) {
-    int rc = check_world(Bg, world, nentity);
+    int rc = check_world(Bg, world, nentity, /*empty_ranks=*/!bucket && !bucket_start);
     if (rc) return rc;
     if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH)
         return set_error(KGE_EINVAL, "kge_shard_plan: mode must be 0 (head-batch) or 1 (tail-batch)");
@@ -579,7 +583,7 @@ int kge_shard_gather_queries(const float* shard, int64_t shard_rows, int64_t ld,
         shard_rows < 0)
         return set_error(KGE_EINVAL, "kge_shard_gather_queries: bad shape");
     if (Bg == 0) return set_error(0, "");
-    if (!shard || !pos || !qown || !qslot || !summary || !qidx)
+    if ((!shard && shard_rows > 0) || !pos || !qown || !qslot || !summary || !qidx)  // no rows: nothing to point at
         return set_error(KGE_EINVAL, "kge_shard_gather_queries: null pointer");
     int qc0, qc1, pcol;
     const int ncol = query_cols(mode, flags, qc0, qc1, pcol);

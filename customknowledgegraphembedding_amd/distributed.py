@@ -59,8 +59,17 @@ from .model import _dims_for
 
 
 # widest per-half dimension the row-sharded train kernels take (kge_shard_train_*: kFwdGradMaxG float4
-# groups per lane, six accumulators per element in registers); wider models train on the dense path
+# groups per lane, six accumulators per element in registers); wider models train on the dense path. This is
+# the limit of ShardedKGE's own dense, 16-B aligned tables; the C ABI's is D / V <= 256 (512 floats where a
+# layout leaves 8-byte, 256 where it leaves 4-byte vectors: include/kge_hip.h)
 SHARD_MAX_D = 1024
+
+
+def shard_max_d(D: int) -> int:
+    """The widest per-half dimension the row-sharded train step takes for dense tables of per-half width D:
+    SHARD_MAX_D where D is a multiple of 4 (16-byte vectors), half of it for other even D, a quarter for odd D.
+    kge_shard_train_* refuse wider ones (KGE_ENOTSUP) and have no unfused fallback."""
+    return SHARD_MAX_D // 4 * (4 if D % 4 == 0 else 2 if D % 2 == 0 else 1)
 
 
 def shard_bounds(nentity: int, world: int, rank: int):

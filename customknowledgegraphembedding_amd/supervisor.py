@@ -111,15 +111,16 @@ class Trainer:
         self.fused = bool(fused)
         self.sharded = None
         if replicas > 1:
-            from .distributed import SHARD_MAX_D, ShardedKGE, warn_dense_fallback
+            from .distributed import ShardedKGE, shard_max_d, warn_dense_fallback
             if self.fused and fused == "split":
                 raise ValueError("fused='split' is single-replica only")
             D = int(getattr(model, "_D", 0))
-            if self.fused and D > SHARD_MAX_D:
+            if self.fused and D > shard_max_d(D):
                 # the row-sharded kernels keep six accumulators per element in registers (D <= 1024
-                # per half); the dense all-reduce path below has no such limit
+                # per half, 512 / 256 where D allows only 8- / 4-byte vectors); the dense all-reduce path
+                # below has no such limit
                 self.fused = False
-                warn_dense_fallback(model, replicas, f"per-half width {D} > {SHARD_MAX_D}")
+                warn_dense_fallback(model, replicas, f"per-half width {D} > {shard_max_d(D)}")
             elif self.fused:
                 self.sharded = ShardedKGE.from_model(model, kernels=shard_kernels)
             else:

@@ -361,8 +361,11 @@ def rejection_cases():
     sh("kge_shard_train_backward", wsb="shard-ws-minus-1")
     sh("kge_shard_train_backward", tail=[P, P, None, P, P, P, P, 0.001, 0.9, 0.999, 1e-8, 0, 0])   # step 0
     sh("kge_shard_train_backward", tail=[P, None, None, P, P, P, P, 0.001, 0.9, 0.999, 1e-8, 1, 0])  # loss NULL
-    # run_score's own rejection, reached with no owned rows (no memset before it): 8 groups per lane
+    # the step's width limit (D / V <= 256; here 8 groups of 4 floats per lane), which all three calls check
+    # ahead of their first memset or launch
     sh("kge_shard_train_forward", rows=0, D=2048)
+    sh("kge_shard_train_combine", rows=0, D=2048), sh("kge_shard_train_backward", rows=0, D=2048)
+    sh("kge_shard_train_forward", D=1028), sh("kge_shard_train_forward", qent=U4, D=260)  # V 4, V 1: 5 groups
     return c
 
 

@@ -1,7 +1,8 @@
 """Helpers of the vector-width and leading-dimension tests (test_widths_gpu.py, test_strides_gpu.py,
-test_strided_cpu.py): non-dense views of tables, ids and outputs, a Python restatement of the library's
-width choice (pick_vg, csrc/kge_abi.hip), and small seeded cases shared by those tests. A plain module:
-nothing here is a fixture or changes how the suite is collected."""
+test_shard_widths_gpu.py, test_strided_cpu.py): non-dense views of tables, ids and outputs, a Python
+restatement of the library's width choice (pick_vg, csrc/kge_abi.hip), small seeded cases shared by those
+tests, and the replica loss the row-sharded train step is held to. A plain module: nothing here is a fixture or
+changes how the suite is collected."""
 import numpy as np
 import torch
 
@@ -37,6 +38,33 @@ def make_case(name, D, E, R, B, N, seed=0, gamma=11.0):
     # the modulus as the fp32 value the library receives (the oracle runs in fp64 on the same fp32 values)
     return dict(name=name, D=D, E=E, R=R, B=B, N=N, ent=ent, rel=rel, pos=pos, neg=neg, w=w, gamma=gamma, rng=rng,
                 mod=float(np.float32(0.5 * rng)))
+
+
+def replica_loss(name, ent, rel, pos, neg, w, mode, gamma, rng, red="tf", T=1.0, keep=None, pos_keep=None):
+    """One replica's train loss (supervisor.py:17-23) with the reduction of the negative branch as a parameter,
+    for the row-sharded step's three forward instantiations: red "tf" is O.tf_train_loss at temperature T (the
+    softmax weights carry gradient), "detached" is O.upstream_train_loss(adversarial=True, temperature=T),
+    "mean" is O.upstream_train_loss(adversarial=False) (tests/test_strided_cpu.py holds it to them).
+    keep [B, N] bool / pos_keep [B] bool state include/kge_hip.h's rule for ids without an owner: a dropped
+    candidate is left out of the row's softmax, or adds 0 to the mean's sum, which is still divided by N; a
+    dropped positive scores 0 and carries no gradient. The ids at dropped places must be valid (any row: its
+    score is computed and discarded). Returns (loss, reduced negatives [B], positive scores [B])."""
+    s = O.score(name, ent, rel, pos, neg, mode, gamma, rng)
+    ps = O.score(name, ent, rel, pos, neg, 3, gamma, rng)[:, 0]
+    if keep is None:
+        keep = torch.ones_like(s, dtype=torch.bool)
+    ls = torch.where(keep, torch.nn.functional.logsigmoid(-s), torch.zeros_like(s))
+    if red == "mean":
+        n = ls.sum(1) / s.shape[1]
+    else:
+        p = torch.softmax((T * s).masked_fill(~keep, float("-inf")), 1)
+        p = torch.where(keep, p, torch.zeros_like(p))  # (a row with nothing kept reduces to 0)
+        n = ((p.detach() if red == "detached" else p) * ls).sum(1)
+    if pos_keep is not None:
+        ps = torch.where(pos_keep, ps, torch.zeros_like(ps))
+    w = w.reshape(-1)
+    loss = (-(w * torch.nn.functional.logsigmoid(ps)).sum() / w.sum() - (w * n).sum() / w.sum()) / 2
+    return loss, n, ps
 
 
 # ------------------------------------------------------------------------------------------------
@@ -118,8 +146,9 @@ def like_table(t, fill=None):
 # ------------------------------------------------------------------------------------------------
 def expected_vg(D, lds=(), offs=(), ptrs=()):
     """pick_vg (csrc/kge_abi.hip): the widest vector width V in {4, 2, 1} that divides D, every leading
-    dimension and rel_off and whose byte size divides every table base address; then the register depth
-    G = pow2ceil(ceil(D / V / 64)). G > 8 is refused by the library (KGE_ENOTSUP)."""
+    dimension and rel_off and whose byte size divides every table base address (for the sharded train step
+    also qent_pos' and dq's); then the register depth G = pow2ceil(ceil(D / V / 64)). G > 8 is refused by the
+    library (KGE_ENOTSUP), G > 4 by the fused train kinds."""
     V = 1
     for v in (4, 2, 1):
         if D % v == 0 and all(x % v == 0 for x in lds) and all(x % v == 0 for x in offs) and \

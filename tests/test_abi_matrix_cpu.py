@@ -1,8 +1,10 @@
 """The host layer of libkge_hip.so answers what it answered before its dispatch was refactored (CPU only).
 
 tests/golden/abi_matrix.json was recorded by tests/golden/make_abi_matrix.py from a build of the commit before
-the refactor (its "recorded_from" names it) and is never regenerated from the code under test. It holds the
-library's own output for
+the refactor (its "recorded_from" names it) and is never regenerated from the code under test, with one kind of
+exception: a change that alters an answer on purpose re-records the file and reviews the difference entry by entry
+(last: the sharded train step's width refusal, one message changed and four cases added, nothing else). It holds
+the library's own output for
   (a) the size and order queries over all six functions x D {4 .. 2048} x B {0 .. 512} x N {1 .. 65536} x
       nentity {0, 1000, 2^28};
   (b) kge_step_planner_get of every `what` after each valid and invalid set_form / set_lead / set_board /

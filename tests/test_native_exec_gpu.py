@@ -117,6 +117,28 @@ def test_loopback_ranks_bitwise(name, W, K, one):
         group.close()
 
 
+@pytest.mark.parametrize("name", ["InterHT", "DistMult"])
+@pytest.mark.parametrize("d,vg", [(33, (1, 1)), (450, (2, 4))])
+def test_loopback_narrow_vector_widths(name, d, vg):
+    """Two loopback ranks at widths whose rows allow only 4- and 8-byte vectors (V = 1 and V = 2 instances of the
+    bucket scorer and of the unsharded kernels it must equal bitwise)."""
+    from tests import strided as S
+
+    E, R, Bh, N, W = 997, 5, 4, 150, 2
+    m = _model(name, E, R, d)
+    group = LoopbackGroup(W)
+    try:
+        ranks = _native_ranks(m, W, group)
+        assert S.table_vg(name, d, m.entity_embedding, m.relation_embedding) == vg
+        assert all(S.table_vg(name, d, sk.shard, sk.relation_embedding) == vg for sk in ranks)
+        _check(m, ranks, [(*_batch(E, R, W * Bh, N, seed=20 + s), s % 2) for s in range(2)], 2)
+        for sk in ranks:
+            for ex in sk._native.values():
+                ex.close()
+    finally:
+        group.close()
+
+
 @pytest.mark.parametrize("name", ["TransE", "ComplEx"])
 def test_loopback_small_n_every_layout(name):
     """N < 128 and the other split layouts: 3 ranks, one chunk per home."""

@@ -11,6 +11,9 @@ import customknowledgegraphembedding_amd as kge
 from customknowledgegraphembedding_amd import ops
 from customknowledgegraphembedding_amd._lib import FN_IDS
 from customknowledgegraphembedding_amd.distributed import ShardedKGE, ThreadComm, run_threads
+from oracle import kge_oracle as O
+from tests import strided as S
+from tests.conftest import rel_close
 from tests.shard_oracle_backend import OracleShardKernels
 
 pytestmark = pytest.mark.gpu
@@ -77,13 +80,16 @@ def test_plan_matches_restatement(W, K, mode, flags, N):
                 assert key(gb[g, lo:hi]) == key(want.bucket[g, lo:hi]), (sk.rank, g, x)
 
 
-def _check_world(name, W, K, E, R, d, Bh, N, seed, bad=False):
+def _check_world(name, W, K, E, R, d, Bh, N, seed, bad=False, vg=None):
     m = _model(name, E, R, d)
     fn = FN_IDS[name]
     ent, rel = m.entity_embedding.detach(), m.relation_embedding.detach()
     mod = float(m.modulus.detach().reshape(-1)[0]) if name == "pRotatE" else 0.0
     pos, neg = _batch(E, R, W * Bh, N, seed, bad)
     ranks = _ranks(m, W)
+    if vg is not None:  # the table and every shard get the same (V, G) instance: the scores can be bitwise equal
+        assert S.table_vg(name, m._D, ent, rel) == vg
+        assert all(S.table_vg(name, sk.D, sk.shard, sk.relation_embedding) == vg for sk in ranks)
     for mode in (0, 1):
         outs = run_threads([lambda sk=sk: sk.step_forward(pos, neg, mode, chunks=K) for sk in ranks])
         torch.cuda.synchronize()
@@ -112,6 +118,53 @@ def test_sharded_forward_bitwise_xcd_order(name, W, K):
     """N >= 128: the unsharded reference is the XCD-sliced kernel (compact ranks carried through the
     bucket scorer's per-run row sort)."""
     _check_world(name, W, K, E=5003, R=5, d=64, Bh=8, N=300, seed=2)
+
+
+# per-half width -> (V, G): every V = 1 and V = 2 instance of the forward kinds (KIND_SHARD_BUCKET,
+# KIND_SCORE_SHARD_XCD and the unsharded kernels they are compared with), which go up to kMaxG = 8
+NARROW = {33: (1, 1), 50: (2, 1), 101: (1, 2), 255: (1, 4), 450: (2, 4), 511: (1, 8), 1022: (2, 8)}
+
+
+@pytest.mark.parametrize("name", list(CFG))
+@pytest.mark.parametrize("d", list(NARROW))
+@pytest.mark.parametrize("N", [37, 150])
+def test_sharded_forward_bitwise_narrow_vector_widths(name, d, N):
+    """Three ranks, one chunk per home, at the widths whose rows allow only 8- or 4-byte vectors; N = 37 for the
+    bucket scorer's short runs, N = 150 for the XCD-sliced order."""
+    _check_world(name, 3, 3, E=997, R=6, d=d, Bh=4, N=N, seed=d, vg=NARROW[d])
+
+
+@pytest.mark.parametrize("name", ["InterHT", "ComplEx", "TransE"])
+@pytest.mark.parametrize("pad", [1, 2])
+def test_sharded_forward_on_padded_shards(name, pad):
+    """Every rank's shard and relation table replaced by row-padded views (NaN padding; V = 1 at pad 1, V = 2 at
+    pad 2): every HipShardKernels call passes its tensors' strides, so the step's scores and reductions stay
+    within the score bar of the fp64 oracle and the padding keeps its bits."""
+    E, R, D, W, Bh, N = 997, 6, 64, 3, 4, 150
+    m = _model(name, E, R, D)
+    pos, neg = _batch(E, R, W * Bh, N, seed=pad)
+    ranks = _ranks(m, W)
+    for sk in ranks:
+        sk.shard = S.padded(sk.shard.cpu(), pad, DEV)
+        sk.relation_embedding = S.padded(sk.relation_embedding.cpu(), pad, DEV)
+        assert S.table_vg(name, D, sk.shard, sk.relation_embedding) == ({1: 1, 2: 2}[pad], 1)
+    views = [t for sk in ranks for t in (sk.shard, sk.relation_embedding)]
+    before = [S.outside_bits(v) for v in views]
+    e64, r64 = m.entity_embedding.detach().cpu().double(), m.relation_embedding.detach().cpu().double()
+    for mode in (0, 1):
+        outs = run_threads([lambda sk=sk: sk.step_forward(pos, neg, mode, chunks=W) for sk in ranks])
+        torch.cuda.synchronize()
+        s_ref = O.score(name, e64, r64, pos.cpu(), neg.cpu(), mode, m._gamma_f, m._range_f)
+        p_ref = O.score(name, e64, r64, pos.cpu(), neg.cpu(), 3, m._gamma_f, m._range_f)
+        n_ref, lp_ref = O.adv_reduce(s_ref)[:, 0], torch.nn.functional.logsigmoid(p_ref)[:, 0]
+        for r, (o_neg, o_pos, s) in enumerate(outs):
+            sl = slice(r * Bh, (r + 1) * Bh)
+            errs = (rel_close(s.cpu().numpy(), s_ref[sl].numpy()), rel_close(o_neg.cpu().numpy(), n_ref[sl].numpy()),
+                    rel_close(o_pos.cpu().numpy(), lp_ref[sl].numpy()))
+            print((name, pad, mode, r), "scores / out_neg / out_pos err", errs)
+            assert max(errs) <= 1e-4, (mode, r, errs)
+    for i, (v, b) in enumerate(zip(views, before)):
+        assert torch.equal(S.outside_bits(v), b), f"view {i}: padding written"
 
 
 def test_sharded_forward_ids_without_owner():

@@ -136,3 +136,44 @@ def test_expected_vg_names_the_issue_instances():
     assert S.expected_vg(520, lds=(522,), ptrs=(4096,)) == (2, 8)
     assert S.expected_vg(520, lds=(521,), ptrs=(4096,))[1] > S.K_MAX_G
     assert S.expected_vg(512, lds=(513,), ptrs=(4096,)) == (1, 8)
+
+
+@pytest.mark.parametrize("name", ["TransE", "DistMult", "ComplEx", "RotatE", "InterHT"])
+@pytest.mark.parametrize("mode", [0, 1])
+def test_replica_loss_is_the_oracles_loss(name, mode):
+    """S.replica_loss (the reference of tests/test_shard_widths_gpu.py) equals O.tf_train_loss at T = 1 and
+    O.upstream_train_loss in both of its reductions at T = 0.5, values and gradients, in fp64; and a candidate
+    that is dropped counts like one that was never in the row (softmax) or like a zero term (mean)."""
+    from oracle import kge_oracle as O
+
+    c = S.make_case(name, 12, 17, 3, 5, 9, seed=mode)
+    w = c["w"].double()
+
+    def both(f):
+        e, r = c["ent"].double().requires_grad_(True), c["rel"].double().requires_grad_(True)
+        loss = f(e, r)
+        loss.backward()
+        return loss.item(), e.grad, r.grad
+
+    def same(a, b):
+        assert a[0] == pytest.approx(b[0], rel=1e-12)
+        for x, y in zip(a[1:], b[1:]):
+            assert float((x - y).abs().max()) <= 1e-12 * max(float(y.abs().max()), 1.0)
+
+    args = (c["pos"], c["neg"], w)
+    same(both(lambda e, r: S.replica_loss(name, e, r, *args, mode, c["gamma"], c["rng"])[0]),
+         both(lambda e, r: O.tf_train_loss(name, e, r, *args, [mode], c["gamma"], c["rng"])))
+    for red, adv in (("detached", True), ("mean", False)):
+        same(both(lambda e, r: S.replica_loss(name, e, r, *args, mode, c["gamma"], c["rng"], red, 0.5)[0]),
+             both(lambda e, r: O.upstream_train_loss(name, e, r, *args, mode, c["gamma"], c["rng"], adversarial=adv,
+                                                     temperature=0.5)))
+    # dropping the last two candidates of every row: the softmax forms equal the loss of the shorter rows
+    keep = torch.ones(5, 9, dtype=torch.bool)
+    keep[:, 7:] = False
+    short = (c["pos"], c["neg"][:, :7], w)
+    same(both(lambda e, r: S.replica_loss(name, e, r, *args, mode, c["gamma"], c["rng"], "tf", 0.5, keep)[0]),
+         both(lambda e, r: S.replica_loss(name, e, r, *short, mode, c["gamma"], c["rng"], "tf", 0.5)[0]))
+    full = S.replica_loss(name, c["ent"].double(), c["rel"].double(), *short, mode, c["gamma"], c["rng"], "mean")[1]
+    drop = S.replica_loss(name, c["ent"].double(), c["rel"].double(), *args, mode, c["gamma"], c["rng"], "mean",
+                          keep=keep)[1]
+    assert torch.allclose(drop * 9, full * 7, rtol=1e-12, atol=0)

@@ -87,6 +87,10 @@ def test_trainer_multi_replica_selection():
     tr, warns = _trainer("InterHT", SHARD_MAX_D + 1, 2)
     assert not tr.fused and tr.sharded is None
     assert len(warns) == 1 and "dense-gradient" in warns[0] and "MB" in warns[0] and "1025" in warns[0]
+    # the kernels' limit is D / V <= 256: widths that leave 8- or 4-byte vectors stop at 512 and 256
+    for hidden, sharded in ((510, True), (514, False), (255, True), (257, False), (511, False), (1022, False)):
+        tr, warns = _trainer("InterHT", hidden, 2)
+        assert (tr.sharded is not None) == sharded and tr.fused == sharded and len(warns) == (0 if sharded else 1), hidden
     tr, warns = _trainer("pRotatE", 8, 2)
     assert tr.sharded is None and len(warns) == 1 and "dense-gradient" in warns[0]
     tr, warns = _trainer("InterHT", SHARD_MAX_D + 1, 1)  # one replica: kge_train_step handles any width
