@@ -8,6 +8,7 @@ called through ctypes on torch's current stream. There is no CPU / eager fallbac
 from ._lib import FN_IDS, HEAD_BATCH, SINGLE, TAIL_BATCH, KGEHipError, build_id, load  # noqa: F401
 from .model import KGEModel, TFKGEModel  # noqa: F401
 from . import ops  # noqa: F401
+from . import evaluate  # noqa: F401  (test_step, predict)
 
-__all__ = ["TFKGEModel", "KGEModel", "ops", "load", "build_id", "KGEHipError", "FN_IDS",
+__all__ = ["TFKGEModel", "KGEModel", "ops", "evaluate", "load", "build_id", "KGEHipError", "FN_IDS",
            "HEAD_BATCH", "TAIL_BATCH", "SINGLE"]

@@ -621,6 +621,11 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
             if (p.tile_rows < 1 || p.rk.chunks < 1 || p.tile_lds > kTileLdsMax) return fail(KGE_EINVAL, "sweep plan missing");
             waves = (p.B + p.tile_rows - 1) / p.tile_rows * 8 * p.rk.chunks * kWavesPerBlock;
             break;
+        case GRID_TOPK_SWEEP:
+            if (p.tile_rows < 1 || p.tk.chunks < 1 || p.tile_lds > kTileLdsMax || p.tk.k < 1 || p.tk.k > kTopkMax || !p.tk.parts)
+                return fail(KGE_EINVAL, "sweep plan missing");
+            waves = (p.B + p.tile_rows - 1) / p.tile_rows * 8 * p.tk.chunks * kWavesPerBlock;
+            break;
     }
     const int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > INT32_MAX) return fail(KGE_EINVAL, "problem too large for one launch");
@@ -1592,6 +1597,75 @@ int kge_eval_rank_sweep(int fn, int mode, const float* ent, int64_t nentity, int
     if (rc) return rc;
     launch_rank_finish(B, nentity, truth, filter_ptr, filter_ids, workspace, ranks, (hipStream_t)stream);
     return check_launch("kge_eval_rank_sweep");
+}
+
+int64_t kge_eval_topk_sweep_workspace_size(int64_t B, int64_t k) {
+    if (B < 0 || B > INT32_MAX || k < 1 || k > kTopkMax) return 0;
+    return (topk_ws_lists(B) * k * 8 + 15) / 16 * 16;
+}
+
+int kge_eval_topk_sweep(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
+                        int64_t nrelation, int64_t rel_ld, int64_t rel_off, const int64_t* pos, int64_t B, int64_t D,
+                        float gamma, float emb_range, float modulus, const int64_t* excl_ptr, const int64_t* excl_ids,
+                        int64_t nexcl, int64_t k, int64_t* out_ids, int64_t ids_ld, float* out_scores,
+                        int64_t scores_ld, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!valid_fn(fn)) return fail(KGE_EINVAL, "unknown score function id " + std::to_string(fn));
+    if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH)
+        return fail(KGE_EINVAL, "kge_eval_topk_sweep: mode must be 0 (head-batch) or 1 (tail-batch)");
+    if (k < 1 || k > kTopkMax) return fail(KGE_EINVAL, "kge_eval_topk_sweep: k must be 1 .. " + std::to_string(kTopkMax));
+    if (B < 0 || D <= 0 || nentity <= 0 || nrelation <= 0 || nexcl < 0) return fail(KGE_EINVAL, "bad shape");
+    if (fn == KGE_DISTMULT || fn == KGE_COMPLEX)
+        return fail(KGE_ENOTSUP, "kge_eval_topk_sweep: DistMult / ComplEx select from the score matrix (kge_topk_rows)");
+    if (B == 0) return ok();
+    if (!ent || !rel || !pos || !out_ids || !out_scores || !workspace || (nexcl > 0 && (!excl_ptr || !excl_ids)))
+        return fail(KGE_EINVAL, "null pointer");
+    if (B > INT32_MAX || nentity > INT32_MAX || ids_ld < k || scores_ld < k || !aligned(workspace, 16))
+        return fail(KGE_EINVAL, "kge_eval_topk_sweep: int32 shapes, row strides >= k and a 16-B aligned workspace");
+    if ((int64_t)workspace_bytes < kge_eval_topk_sweep_workspace_size(B, k))
+        return fail(KGE_EINVAL, "kge_eval_topk_sweep: workspace too small");
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
+    ScoreParams p;
+    fill_indexed(p, t, {mode, pos, nullptr, 0, B, nentity});
+    int V = 1, G = 1;
+    int rc = pick_vg(p, V, G);
+    if (rc) return rc;
+    if (G > kSweepMaxG) return fail(KGE_ENOTSUP, "kge_eval_topk_sweep: per-half dim past " + std::to_string(kSweepMaxG * kWave * V));
+    if (nexcl == 0) excl_ptr = excl_ids = nullptr;
+    // query rows per block: the rows' operand images, every wave's list of k entries per row and the row's exclusion
+    // range within one block's LDS, at most kSweepMaxRows
+    const int64_t row_lds = (int64_t)shard_nq(fn) * G * kWave * V * 4 + (int64_t)kSweepWaves * k * 8 + 16;
+    const int64_t R = std::min<int64_t>(std::min<int64_t>(kSweepMaxRows, B), kTileLdsMax / row_lds);
+    if (R < 1) return fail(KGE_ENOTSUP, "kge_eval_topk_sweep: one query row does not fit the LDS");
+    const int64_t groups = (B + R - 1) / R, S = (nentity + 7) / 8;
+    const int64_t chunks = sweep_chunks(groups, S);
+    if (B * 8 * chunks > topk_ws_lists(B)) return fail(KGE_EINVAL, "kge_eval_topk_sweep: workspace bound");
+    p.tile_rows = (int)R;
+    p.tile_lds = (int)(R * row_lds);
+    p.tk.xptr = excl_ptr;
+    p.tk.xids = excl_ids;
+    p.tk.k = (int)k;
+    p.tk.chunks = (int)chunks;
+    p.tk.parts = static_cast<int2*>(workspace);
+    rc = run_score(fn, mode, p, KIND_TOPK_SWEEP, stream);
+    if (rc) return rc;
+    launch_topk_merge(workspace, B, 8 * chunks, (int)k, out_ids, ids_ld, out_scores, scores_ld, (hipStream_t)stream);
+    return check_launch("kge_eval_topk_sweep");
+}
+
+int kge_topk_rows(const float* scores, int64_t M, int64_t N, int64_t ld, const int64_t* excl_ptr,
+                  const int64_t* excl_ids, int64_t nexcl, int64_t k, int64_t* out_ids, int64_t ids_ld,
+                  float* out_scores, int64_t scores_ld, void* stream) {
+    if (k < 1 || k > kTopkMax) return fail(KGE_EINVAL, "kge_topk_rows: k must be 1 .. " + std::to_string(kTopkMax));
+    if (M < 0 || N < 0 || nexcl < 0) return fail(KGE_EINVAL, "bad shape");
+    if (M == 0) return ok();
+    if ((!scores && N > 0) || !out_ids || !out_scores || (nexcl > 0 && (!excl_ptr || !excl_ids)))
+        return fail(KGE_EINVAL, "null pointer");
+    if (M > INT32_MAX || N > INT32_MAX || ld < N || ids_ld < k || scores_ld < k)
+        return fail(KGE_EINVAL, "kge_topk_rows: int32 shapes, ld >= N and output row strides >= k");
+    if (nexcl == 0) excl_ptr = excl_ids = nullptr;
+    launch_topk_rows(scores, M, N, ld, excl_ptr, excl_ids, (int)k, out_ids, ids_ld, out_scores, scores_ld,
+                     (hipStream_t)stream);
+    return check_launch("kge_topk_rows");
 }
 
 int kge_score_dense(int fn, int mode, const float* head, int64_t head_ld, const float* rel, int64_t rel_ld,

@@ -3900,6 +3900,186 @@ __global__ __launch_bounds__(NWV * kWave) void rank_sweep_kernel(ScoreParams p) 
     if (t < nr && cl[t]) atomicAdd(&p.rk.cnt[g0 + t], cl[t]);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Exact filtered top-k (kge_eval_topk_sweep, kge_topk_rows). A list is held by one wave, one (score, id) entry per
+// lane: lane j the j-th best in the lists' order (score descending, ties by ascending id: a total order, so the k
+// best of a set do not depend on how the set was cut up or in which order it was seen), empty slots
+// (-inf, kTopkEmpty) last. Everything the waves decide on is wave-uniform, so no lane diverges.
+//   topk_offer: a candidate is compared with the list's k-th entry first; only one that is ahead of it is looked
+//   up in the row's exclusion range (binary search on the ascending ids) and then inserted: one ballot of the
+//   entries ahead of it, a popcount for its position, the entries behind move up one lane. A NaN score is ahead of
+//   nothing.
+//   topk_merge: a second sorted list's entries offered in order, until one is not ahead of the k-th entry (the
+//   rest of that list is behind it too).
+// topk_sweep_kernel is rank_sweep_kernel's decomposition (block = entity slice x row group x chunk, two candidate
+// rows per wave in registers, query images in LDS) with a list per (wave, query row) in LDS ([NWV][R][k], each lane
+// reading and writing its own slot only) where that kernel counts, and the lists' k-th entries in registers (lane
+// r: row r's): a candidate that is not ahead of the k-th entry reads no list. At the sweep's end wave w merges the
+// waves' lists of row w and stores the block's list of each row at parts[row][chunk * 8 + slice][k]; a block with
+// no entity rows stores empty lists, so the workspace needs no preparation. topk_merge_kernel (kge_eval.hip) merges
+// a row's lists.
+// ---------------------------------------------------------------------------------------------
+// an empty slot (by value: a named one selected against a load would live in scratch)
+__device__ __forceinline__ int2 topk_none() { return make_int2(__float_as_int(-INFINITY), kTopkEmpty); }
+
+__device__ __forceinline__ bool topk_ahead(float sa, int ia, float sb, int ib) {
+    return sa > sb || (sa == sb && ia < ib);
+}
+
+// whether e is among the ascending ids[lo, hi)
+__device__ __forceinline__ bool topk_listed(const int64_t* __restrict__ ids, int64_t lo, int64_t hi, int64_t e) {
+    int64_t a = lo, b = hi;
+    while (a < b) {
+        const int64_t mid = (a + b) >> 1;
+        if (ids[mid] < e) a = mid + 1; else b = mid;
+    }
+    return a < hi && ids[a] == e;
+}
+
+__device__ __forceinline__ void topk_insert(float& ms, int& mi, float s, int e, int lane) {
+    const int pos = __popcll(__ballot(topk_ahead(ms, mi, s, e)));  // the entries ahead: lanes 0 .. pos - 1
+    const float us = __shfl_up(ms, 1);
+    const int ui = __shfl_up(mi, 1);
+    if (lane > pos) {
+        ms = us;
+        mi = ui;
+    } else if (lane == pos) {
+        ms = s;
+        mi = e;
+    }
+}
+
+// offers the wave-uniform candidate (s, e) to the list; true when the list changed
+__device__ __forceinline__ bool topk_offer(float& ms, int& mi, float s, int e, int k, int lane,
+                                           const int64_t* __restrict__ xids, int64_t xlo, int64_t xhi) {
+    s = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s)));
+    e = __builtin_amdgcn_readfirstlane(e);
+    const float ts = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ms), k - 1));
+    const int ti = __builtin_amdgcn_readlane(mi, k - 1);
+    if (!topk_ahead(s, e, ts, ti)) return false;
+    if (xids && topk_listed(xids, xlo, xhi, e)) return false;
+    topk_insert(ms, mi, s, e, lane);
+    return true;
+}
+
+// merges the sorted list (cs, ci) (one entry per lane, the first k count) into (ms, mi)
+__device__ __forceinline__ void topk_merge(float& ms, int& mi, float cs, int ci, int k, int lane) {
+    for (int j = 0; j < k; ++j) {
+        const float s = __shfl(cs, j);
+        const int e = __shfl(ci, j);
+        if (!topk_offer(ms, mi, s, e, k, lane, nullptr, 0, 0)) break;
+    }
+}
+
+template <int FN, bool CH, int V, int G, int NWV>
+__global__ __launch_bounds__(NWV * kWave) void topk_sweep_kernel(ScoreParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char topk_smem[];
+    constexpr int NQ = shard_nq(FN);  // operand images per query row
+    constexpr int W = G * kWave;
+    static_assert(kSweepMaxRows <= NWV, "one merging wave per query row");
+    const int R = p.tile_rows, K = p.tk.k;
+    vecf<V>* qimg = reinterpret_cast<vecf<V>*>(topk_smem);               // [R][NQ][W]
+    int2* lst = reinterpret_cast<int2*>(qimg + (size_t)R * NQ * W);      // [NWV][R][K] (score bits, id)
+    int64_t* xr = reinterpret_cast<int64_t*>(lst + (size_t)NWV * R * K); // [R][2] the rows' exclusion ranges
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int x = (int)(blockIdx.x & 7);
+    const int64_t groups = (p.B + R - 1) / R, rest = blockIdx.x >> 3;
+    const int64_t ck = rest / groups, g0 = (rest - ck * groups) * R;
+    const int nr = (int)min<int64_t>(R, p.B - g0);
+    const int64_t S = (p.c_rows + 7) / 8;
+    const int64_t e_lo = min((int64_t)x * S, p.c_rows), e_hi = min(p.c_rows, e_lo + S);
+    const int64_t CS = (S + p.tk.chunks - 1) / p.tk.chunks;
+    const int64_t lo = min(e_lo + ck * CS, e_hi), hi = min(e_hi, lo + CS);
+    if (nr <= 0 || ck >= p.tk.chunks) return;  // block-uniform
+    const int64_t nparts = 8 * (int64_t)p.tk.chunks, part = ck * 8 + x;
+    const int2 none = topk_none();
+    if (lo >= hi) {  // block-uniform (an empty slice or chunk): empty lists
+        for (int i = t; i < nr * K; i += NWV * kWave) {
+            const int r = i / K;
+            p.tk.parts[((g0 + r) * nparts + part) * K + (i - r * K)] = none;
+        }
+        return;
+    }
+
+    for (int r = w; r < nr; r += NWV) {
+        Query<FN, CH, V, G> q;
+        int64_t qi, ri;
+        bool qok, rok;
+        build_query_for<FN, CH, V, G>(p, g0 + r, lane, q, qi, ri, qok, rok);
+        vecf<V>* qr = qimg + (size_t)r * NQ * W;
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            qr[lane + k * kWave] = q.q0[k];
+            if constexpr (NQ > 1) qr[W + lane + k * kWave] = q.q1[k];
+            if constexpr (NQ > 2) qr[2 * W + lane + k * kWave] = q.q2[k];
+        }
+    }
+    for (int i = t; i < NWV * R * K; i += NWV * kWave) lst[i] = none;
+    if (t < nr) {
+        xr[2 * t] = p.tk.xptr ? p.tk.xptr[g0 + t] : 0;
+        xr[2 * t + 1] = p.tk.xptr ? p.tk.xptr[g0 + t + 1] : 0;
+    }
+    __syncthreads();
+    int2* const mine = lst + (size_t)w * R * K;  // this wave's lists: lane j reads and writes slot j only
+    float thr_s = -INFINITY;  // lane r: the k-th entry of this wave's list of row r
+    int thr_i = kTopkEmpty;
+    for (int64_t e = lo + w; e < hi; e += 2 * NWV) {
+        const int64_t e1 = e + NWV;
+        const bool has1 = e1 < hi;  // wave-uniform
+        const int id0 = __builtin_amdgcn_readfirstlane((int)e), id1 = __builtin_amdgcn_readfirstlane((int)e1);
+        Cand<FN, V, G> c0, c1;
+        c0.load(p.cent + e * p.c_ld, true, p.D, lane);
+        c1.load(p.cent + (has1 ? e1 : e) * p.c_ld, has1, p.D, lane);
+        cand_prepare<FN, V, G>(c0, p);
+        cand_prepare<FN, V, G>(c1, p);
+        for (int r = 0; r < nr; ++r) {
+            const vecf<V>* qr = qimg + (size_t)r * NQ * W;
+            Query<FN, CH, V, G> q;  // one read of the row's images for both candidates
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                q.q0[k] = qr[lane + k * kWave];
+                if constexpr (NQ > 1) q.q1[k] = qr[W + lane + k * kWave];
+                if constexpr (NQ > 2) q.q2[k] = qr[2 * W + lane + k * kWave];
+            }
+            const float s0 = cand_score_with<FN, CH, V, G, true>(c0, make_float2(0.f, 0.f), q, p);
+            const float s1 = cand_score_with<FN, CH, V, G, true>(c1, make_float2(0.f, 0.f), q, p);
+            // wave-uniform: row r's k-th entry against both scores; the list itself is read only by a candidate
+            // ahead of it
+            const float ts = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(thr_s), r));
+            const int ti = __builtin_amdgcn_readlane(thr_i, r);
+            const float u0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s0)));
+            const float u1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s1)));
+            if (topk_ahead(u0, id0, ts, ti) || (has1 && topk_ahead(u1, id1, ts, ti))) {
+                const int2 my = lane < K ? mine[r * K + lane] : topk_none();
+                float ms = __int_as_float(my.x);
+                int mi = my.y;
+                const int64_t xlo = xr[2 * r], xhi = xr[2 * r + 1];
+                bool changed = topk_offer(ms, mi, u0, id0, K, lane, p.tk.xids, xlo, xhi);
+                if (has1) changed |= topk_offer(ms, mi, u1, id1, K, lane, p.tk.xids, xlo, xhi);
+                if (changed) {
+                    if (lane < K) mine[r * K + lane] = make_int2(__float_as_int(ms), mi);
+                    const float ns = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ms), K - 1));
+                    const int ni = __builtin_amdgcn_readlane(mi, K - 1);
+                    if (lane == r) {
+                        thr_s = ns;
+                        thr_i = ni;
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int r = w; r < nr; r += NWV) {
+        float ms = -INFINITY;
+        int mi = kTopkEmpty;
+        for (int ww = 0; ww < NWV; ++ww) {
+            const int2 o = lane < K ? lst[((size_t)ww * R + r) * K + lane] : topk_none();
+            topk_merge(ms, mi, __int_as_float(o.x), o.y, K, lane);
+        }
+        if (lane < K) p.tk.parts[((g0 + r) * nparts + part) * K + lane] = make_int2(__float_as_int(ms), mi);
+    }
+}
+
 }  // namespace kge_impl
 
 #include "kge_shard.h"
@@ -3998,6 +4178,18 @@ bool launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
                                     hipFuncAttributeMaxDynamicSharedMemorySize, kTileLdsMax) == hipSuccess;
             (void)lds_ok;
             hipLaunchKernelGGL((rank_sweep_kernel<FN, CH, V, G, kSweepWaves>), dim3(blocks), dim3(kSweepWaves * kWave),
+                               p.tile_lds, st, p);
+            return true;
+        }
+        return false;
+    }
+    if (kind == KIND_TOPK_SWEEP) {
+        if constexpr (kind_has(KIND_TOPK_SWEEP, FN, CH, G)) {
+            static const bool lds_ok =
+                hipFuncSetAttribute(reinterpret_cast<const void*>(topk_sweep_kernel<FN, CH, V, G, kSweepWaves>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, kTileLdsMax) == hipSuccess;
+            (void)lds_ok;
+            hipLaunchKernelGGL((topk_sweep_kernel<FN, CH, V, G, kSweepWaves>), dim3(blocks), dim3(kSweepWaves * kWave),
                                p.tile_lds, st, p);
             return true;
         }

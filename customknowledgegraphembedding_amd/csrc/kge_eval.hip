@@ -1202,6 +1202,74 @@ __global__ __launch_bounds__(kBlock) void rank_finish_kernel(int64_t M, int64_t 
     if (lane == 0) ranks[q] = 1 + (int64_t)gcnt[q] - sub;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Exact filtered top-k (kge_device.h: topk_offer / topk_merge, the lists' order and their empty slots).
+//   topk_merge_kernel, one wave per query row: merges the row's `nparts` sorted lists of topk_sweep_kernel's
+//   workspace and writes ids (int64, -1 for an empty slot) and scores.
+//   topk_rows_kernel, one block per row of a score matrix: wave w reads columns 64 w .. 64 w + 63 of every 256, lane
+//   per column; the columns ahead of the wave's k-th entry (a ballot) are offered in ascending column order, each
+//   looked up in the row's exclusion range only then; wave 0 merges the four lists through LDS.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void topk_store(float ms, int mi, int k, int lane, int64_t* __restrict__ ids,
+                                           float* __restrict__ scores) {
+    if (lane < k) {
+        ids[lane] = mi == kTopkEmpty ? -1 : (int64_t)mi;
+        scores[lane] = ms;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void topk_merge_kernel(const int2* __restrict__ parts, int64_t B, int64_t nparts,
+                                                            int k, int64_t* __restrict__ out_ids, int64_t ids_ld,
+                                                            float* __restrict__ out_scores, int64_t scores_ld) {
+    const int64_t b = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (b >= B) return;  // wave-uniform
+    const int lane = threadIdx.x & 63;
+    float ms = -INFINITY;
+    int mi = kTopkEmpty;
+    for (int64_t i = 0; i < nparts; ++i) {
+        const int2 o = lane < k ? parts[(b * nparts + i) * k + lane] : make_int2(__float_as_int(-INFINITY), kTopkEmpty);
+        topk_merge(ms, mi, __int_as_float(o.x), o.y, k, lane);
+    }
+    topk_store(ms, mi, k, lane, out_ids + b * ids_ld, out_scores + b * scores_ld);
+}
+
+__global__ __launch_bounds__(kBlock) void topk_rows_kernel(const float* __restrict__ S, int64_t M, int64_t N, int64_t ld,
+                                                           const int64_t* __restrict__ xptr,
+                                                           const int64_t* __restrict__ xids, int k,
+                                                           int64_t* __restrict__ out_ids, int64_t ids_ld,
+                                                           float* __restrict__ out_scores, int64_t scores_ld) {
+    __shared__ int2 wl[kWavesPerBlock][kWave];
+    const int64_t q = blockIdx.x;
+    if (q >= M) return;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const float* row = S + q * ld;
+    const int64_t xlo = xptr ? xptr[q] : 0, xhi = xptr ? xptr[q + 1] : 0;
+    float ms = -INFINITY;
+    int mi = kTopkEmpty;
+    for (int64_t base = (int64_t)w * kWave; base < N; base += kBlock) {  // wave-uniform
+        const int64_t e = base + lane;
+        const bool in = e < N;
+        const float v = in ? row[e] : 0.f;
+        const float ts = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ms), k - 1));
+        const int ti = __builtin_amdgcn_readlane(mi, k - 1);
+        uint64_t m = __ballot(in && topk_ahead(v, (int)e, ts, ti));  // a NaN is ahead of nothing
+        while (m) {
+            const int j = __ffsll((unsigned long long)m) - 1;
+            m &= m - 1;
+            topk_offer(ms, mi, __shfl(v, j), (int)(base + j), k, lane, xids, xlo, xhi);
+        }
+    }
+    wl[w][lane] = make_int2(__float_as_int(ms), mi);
+    __syncthreads();
+    if (w == 0) {
+        for (int ww = 1; ww < kWavesPerBlock; ++ww) {
+            const int2 o = wl[ww][lane];
+            topk_merge(ms, mi, __int_as_float(o.x), o.y, k, lane);
+        }
+        topk_store(ms, mi, k, lane, out_ids + q * ids_ld, out_scores + q * scores_ld);
+    }
+}
+
 }  // namespace
 
 int launch_gemm_nt_f32x3(const float* A, const float* B, float* C, int M, int N, int K, int64_t lda, int64_t ldb,
@@ -1315,6 +1383,20 @@ int launch_rank_finish(int64_t M, int64_t N, const int64_t* truth, const int64_t
     const float* fs = reinterpret_cast<const float*>(static_cast<const unsigned char*>(ws) + ((M * 8 + 15) / 16 * 16));
     hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)((M + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0,
                        st, M, N, truth, fptr, fids, ts, fs, gcnt, ranks);
+    return 0;
+}
+
+int launch_topk_merge(const void* parts, int64_t B, int64_t nparts, int k, int64_t* out_ids, int64_t ids_ld,
+                      float* out_scores, int64_t scores_ld, hipStream_t st) {
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((B + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st,
+                       static_cast<const int2*>(parts), B, nparts, k, out_ids, ids_ld, out_scores, scores_ld);
+    return 0;
+}
+
+int launch_topk_rows(const float* S, int64_t M, int64_t N, int64_t ld, const int64_t* xptr, const int64_t* xids, int k,
+                     int64_t* out_ids, int64_t ids_ld, float* out_scores, int64_t scores_ld, hipStream_t st) {
+    hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)M), dim3(kBlock), 0, st, S, M, N, ld, xptr, xids, k, out_ids,
+                       ids_ld, out_scores, scores_ld);
     return 0;
 }
 

@@ -39,6 +39,7 @@ enum Kind {
     KIND_SCORE_TILE = 20,      // kge_score_indexed in the same order (no positives)
     KIND_RANK_PAIRS = 21,      // kge_eval_rank_sweep: the truths' and the filter entries' scores (one wave per pair)
     KIND_RANK_SWEEP = 22,      // kge_eval_rank_sweep: every entity row against a group of query rows, counting
+    KIND_TOPK_SWEEP = 23,      // kge_eval_topk_sweep: the same sweep, each wave keeping the best k per query row
     KIND_COUNT
 };
 constexpr int kFwdGradMaxG = 4;  // the fused forward + query gradient keeps 6 accumulators per element
@@ -50,6 +51,23 @@ constexpr int kSweepWaves = 16;
 constexpr int kSweepMaxRows = 16;         // query rows per block
 constexpr int kSweepLdsMax = 144 * 1024;  // operand images of one block
 constexpr int kSweepMinBlocks = 256;      // blocks wanted before an entity slice is cut into chunks (one per CU)
+// topk_sweep_kernel / topk_rows_kernel: a list is one entry per lane; an empty slot is (-inf, kTopkEmpty), behind
+// every real entry in the lists' order (score descending, ties by ascending id)
+constexpr int kTopkMax = KGE_TOPK_MAX;
+constexpr int kTopkEmpty = 0x7fffffff;
+static_assert(kTopkMax <= kWave, "one list entry per lane");
+// chunks per entity slice of a top-k sweep of `groups` row groups over slices of S rows (kge_eval_rank_sweep's
+// rule): a grid of fewer than kSweepMinBlocks blocks cuts every slice into contiguous chunks of at least
+// 2 kSweepWaves rows (one pair of rows per wave)
+inline int64_t sweep_chunks(int64_t groups, int64_t S) {
+    const int64_t want = (kSweepMinBlocks + groups * 8 - 1) / (groups * 8);
+    const int64_t most = S / (2 * kSweepWaves) > 1 ? S / (2 * kSweepWaves) : 1;
+    const int64_t c = want < most ? want : most;
+    return c > 1 ? c : 1;
+}
+// partial lists of the top-k sweep for B query rows: 8 slices x chunks, chunks <= ceil(kSweepMinBlocks / (8 groups))
+// and B <= kSweepMaxRows groups', so B x chunks < kSweepMinBlocks / 8 * kSweepMaxRows + B
+constexpr int64_t topk_ws_lists(int64_t B) { return 8 * ((int64_t)kSweepMinBlocks / 8 * kSweepMaxRows + B); }
 
 // How run_score sizes a kind's grid (kWavesPerBlock waves per counted block; B = p.B, E = p.c_rows)
 enum GridRule {
@@ -64,6 +82,7 @@ enum GridRule {
     GRID_SHARD_EPILOGUE,      // a wave per slot (2 B), one loss block
     GRID_RANK_PAIRS,          // a wave per pair: B truths, then p.rk.nf filter entries
     GRID_RANK_SWEEP,          // a block per (group of p.tile_rows rows, entity slice, chunk of p.rk.chunks)
+    GRID_TOPK_SWEEP,          // the same with p.tk.chunks chunks
 };
 
 // What a kind needs, stated once: run_score checks a launch against its entry and launch_one / launch_shard
@@ -104,6 +123,7 @@ constexpr KindInfo kKinds[KIND_COUNT] = {
     /* KIND_SCORE_TILE */      {GRID_TILE_GROUPS, true, kFwdGradMaxG, false, false, false, "kge score launch"},
     /* KIND_RANK_PAIRS */      {GRID_RANK_PAIRS, true, kSweepMaxG, false, false, false, "kge_eval_rank_sweep", true},
     /* KIND_RANK_SWEEP */      {GRID_RANK_SWEEP, true, kSweepMaxG, false, false, false, "kge_eval_rank_sweep", true},
+    /* KIND_TOPK_SWEEP */      {GRID_TOPK_SWEEP, true, kSweepMaxG, false, false, false, "kge_eval_topk_sweep", true},
 };
 // whether kind k has a (FN, CH, G) instantiation
 constexpr bool kind_has(int k, int fn, bool ch, int G) {
@@ -241,6 +261,14 @@ struct ScoreParams {
         float* fs;             // [nf] the filter entries' scores
         int chunks;            // contiguous chunks an entity slice is cut into (one block per chunk and row group)
     } rk;
+    // kge_eval_topk_sweep (topk_sweep_kernel; tile_rows / tile_lds as for the rank sweep)
+    struct {
+        const int64_t* xptr;  // [B + 1] exclusion CSR, or null
+        const int64_t* xids;
+        int k;
+        int chunks;           // contiguous chunks an entity slice is cut into
+        int2* parts;          // [B][8 chunks][k] (score bits, id): the sorted list of each (row, chunk, slice)
+    } tk;
     float* out;
     int64_t out_ld;
     int64_t B, N;
@@ -356,6 +384,11 @@ int launch_eval_rank_planes(const void* Ap, int64_t a_rows, const void* Bp, int6
 // rank_finish_kernel alone on a workspace of eval_rank_ws_bytes' layout (kge_eval_rank_sweep)
 int launch_rank_finish(int64_t M, int64_t N, const int64_t* truth, const int64_t* fptr, const int64_t* fids, void* ws,
                        int64_t* ranks, hipStream_t st);
+// kge_eval_topk_sweep's merge of `parts` lists per row (topk_sweep_kernel's workspace), and kge_topk_rows
+int launch_topk_merge(const void* parts, int64_t B, int64_t nparts, int k, int64_t* out_ids, int64_t ids_ld,
+                      float* out_scores, int64_t scores_ld, hipStream_t st);
+int launch_topk_rows(const float* S, int64_t M, int64_t N, int64_t ld, const int64_t* xptr, const int64_t* xids, int k,
+                     int64_t* out_ids, int64_t ids_ld, float* out_scores, int64_t scores_ld, hipStream_t st);
 int launch_rank(const float* S, int64_t M, int64_t N, int64_t ld, const int64_t* truth, const int64_t* fptr,
                 const int64_t* fids, int64_t* ranks, hipStream_t st);
 

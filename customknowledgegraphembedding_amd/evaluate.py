@@ -14,6 +14,10 @@ without materialising S (kge_eval_rank_planes: the same ranks), and TransE / Rot
 through rank_sweep (kge_eval_rank_sweep: each entity row loaded once per group of query rows, prepared once and
 compared with every query's truth score on the spot: the same ranks); score_all + rank_filtered remains the
 path of TranSparse and of widths the sweep has no kernel for.
+
+predict answers a query instead of ranking a known truth: the k best entities for (h, r, ?) / (?, r, t) with their
+scores, known answers left out (exact filtered top-k: topk_sweep / kge_eval_topk_sweep for the distance functions,
+score_all + topk_rows / kge_topk_rows otherwise).
 """
 from __future__ import annotations
 
@@ -260,6 +264,179 @@ def rank_sweep(model, positive_sample: torch.Tensor, mode: str, truth: torch.Ten
     return ranks
 
 
+TOPK_MAX = 64  # KGE_TOPK_MAX (include/kge_hip.h)
+_TOPK_WS = {}
+
+
+def build_exclude(queries: np.ndarray, mode: str, triples) -> tuple[np.ndarray, np.ndarray]:
+    """CSR (ptr [M+1], ids) of the answers `triples` already hold for each query: head-batch (?, r, t): every h'
+    with (h', r, t) known; tail-batch (h, r, ?): every t' with (h, r, t') known. build_filter without the removal
+    of the query's own answer (the candidate slot of a query triple is ignored). Ids are distinct and sorted
+    within a row."""
+    by_rt, by_hr = defaultdict(set), defaultdict(set)
+    for h, r, t in triples:
+        by_rt[(int(r), int(t))].add(int(h))
+        by_hr[(int(h), int(r))].add(int(t))
+    queries = np.asarray(queries, dtype=np.int64).reshape(-1, 3)
+    ptr = np.zeros(len(queries) + 1, dtype=np.int64)
+    rows = []
+    for i, (h, r, t) in enumerate(queries):
+        s = by_rt.get((int(r), int(t)), ()) if mode == "head-batch" else by_hr.get((int(h), int(r)), ())
+        rows.append(np.array(sorted(s), dtype=np.int64))
+        ptr[i + 1] = ptr[i] + len(rows[-1])
+    ids = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+    return ptr, ids
+
+
+def _check_k(k, what):
+    if int(k) != k or not 1 <= int(k) <= TOPK_MAX:
+        raise ValueError(f"{what}: k must be in 1 .. {TOPK_MAX}, got {k}")
+    return int(k)
+
+
+def _check_excl(what, dev, rows, excl_ptr, excl_ids, nexcl):
+    """(excl_ptr, excl_ids, nexcl) checked as rank_sweep checks its filter: contiguous int64 tensors on `dev`."""
+    if excl_ptr is None:
+        return None, None, 0
+    for name, t, n in (("excl_ptr", excl_ptr, rows + 1), ("excl_ids", excl_ids, None)):
+        if t is None:
+            continue
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: {name} must be a contiguous int64 tensor on {dev}")
+        if n is not None and t.numel() != n:
+            raise ValueError(f"{what}: {name} has {t.numel()} elements, expected {n}")
+    nx = int(excl_ptr[-1]) if nexcl is None else int(nexcl)
+    if nx > 0 and (excl_ids is None or excl_ids.numel() < nx):
+        raise ValueError(f"{what}: excl_ids shorter than nexcl")
+    if nx == 0:
+        return None, None, 0
+    return excl_ptr, excl_ids, nx
+
+
+def topk_sweep(model, positive_sample: torch.Tensor, mode: str, k: int, excl_ptr: torch.Tensor | None = None,
+               excl_ids: torch.Tensor | None = None, nexcl: int | None = None):
+    """(ids [B, k] int64, scores [B, k]) of the k best entities per query row for TransE / RotatE / pRotatE /
+    InterHT, without the [B, E] score matrix (kge_eval_topk_sweep: rank_sweep's sweep, each wave keeping the best k
+    per query row, then a merge): score descending, ties by ascending id, without the ids of the row's exclusion
+    list (CSR, build_exclude's form; excl_ptr starts at 0, nexcl = excl_ptr[-1], read from the device when not
+    given) and without NaN scores; rows with fewer than k valid entities are padded with id -1 and score -inf. The
+    scores are bitwise score_all's. None where the library has no sweep for the model (DistMult / ComplEx /
+    TranSparse, a per-half width past 1 024): callers fall back to score_all + topk_rows. The index tensors must be
+    int64, contiguous and on the tables' device (ValueError otherwise)."""
+    k = _check_k(k, "topk_sweep")
+    if model.model_name not in FN_IDS:
+        return None
+    ent, rel = model.entity_embedding.detach(), model.relation_embedding.detach()
+    dev = ent.device
+    if positive_sample.dim() != 2 or positive_sample.shape[1] != 3:
+        raise ValueError("topk_sweep: positive_sample must be [B, 3]")
+    B, E = positive_sample.shape[0], ent.shape[0]
+    if positive_sample.dtype != torch.int64 or not positive_sample.is_contiguous() or positive_sample.device != dev:
+        raise ValueError(f"topk_sweep: positive_sample must be a contiguous int64 tensor on {dev}")
+    excl_ptr, excl_ids, nx = _check_excl("topk_sweep", dev, B, excl_ptr, excl_ids, nexcl)
+    ops._need_gpu(ent, rel)
+    lib = _lib.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    key = (str(dev), st)
+    wsb = int(lib.kge_eval_topk_sweep_workspace_size(B, k))
+    ws = _TOPK_WS.get(key)
+    if ws is None or ws.numel() < wsb:
+        ws = _TOPK_WS[key] = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, k), dtype=torch.int64, device=dev)
+    scores = torch.empty((B, k), dtype=torch.float32, device=dev)
+    modulus = float(model.modulus.detach().reshape(-1)[0]) if model.model_name == "pRotatE" else 0.0
+    rc = lib.kge_eval_topk_sweep(FN_IDS[model.model_name], ops.mode_id(mode), ent.data_ptr(), E, ent.stride(0),
+                                 rel.data_ptr(), rel.shape[0], rel.stride(0), model._rel_off,
+                                 positive_sample.data_ptr(), B, model._D, model._gamma_f, model._range_f, modulus,
+                                 None if excl_ptr is None else excl_ptr.data_ptr(),
+                                 None if excl_ids is None else excl_ids.data_ptr(), nx, k, ids.data_ptr(), k,
+                                 scores.data_ptr(), k, ws.data_ptr(), ws.numel(), st)
+    if rc == _ENOTSUP:
+        return None
+    check(rc, "kge_eval_topk_sweep")
+    return ids, scores
+
+
+def topk_rows(scores: torch.Tensor, k: int, excl_ptr: torch.Tensor | None = None,
+              excl_ids: torch.Tensor | None = None, out_ids: torch.Tensor | None = None,
+              out_scores: torch.Tensor | None = None):
+    """(ids [M, k] int64, scores [M, k]) of the k best columns of each row of a [M, N] fp32 score matrix
+    (kge_topk_rows, one block per row), under topk_sweep's contract: the path of score_all's matrix for DistMult /
+    ComplEx / TranSparse and for widths the sweep has no kernel for. `out_ids` / `out_scores`: [M, k] views to
+    write into (any row stride)."""
+    k = _check_k(k, "topk_rows")
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError("topk_rows: scores must be a [M, N] float32 matrix with contiguous rows")
+    ops._need_gpu(scores)
+    M, N = scores.shape
+    dev = scores.device
+    excl_ptr, excl_ids, nx = _check_excl("topk_rows", dev, M, excl_ptr, excl_ids, None)
+    if out_ids is None:
+        out_ids = torch.empty((M, k), dtype=torch.int64, device=dev)
+    if out_scores is None:
+        out_scores = torch.empty((M, k), dtype=torch.float32, device=dev)
+    for name, t, dt in (("out_ids", out_ids, torch.int64), ("out_scores", out_scores, torch.float32)):
+        if t.shape != (M, k) or t.dtype != dt or t.device != dev or (k > 1 and t.stride(1) != 1):
+            raise ValueError(f"topk_rows: {name} must be a [M, k] {dt} tensor with contiguous rows on {dev}")
+    check(_lib.load().kge_topk_rows(scores.data_ptr(), M, N, scores.stride(0),
+                                    None if excl_ptr is None else excl_ptr.data_ptr(),
+                                    None if excl_ids is None else excl_ids.data_ptr(), nx, k, out_ids.data_ptr(),
+                                    out_ids.stride(0), out_scores.data_ptr(), out_scores.stride(0),
+                                    torch.cuda.current_stream(dev).cuda_stream), "kge_topk_rows")
+    return out_ids, out_scores
+
+
+# The functions predict sends through topk_sweep: those whose sweep measured faster than score_all + topk_rows by
+# DESIGN §3.0's rule (§3.4, profiles/r11_topk_ab.txt); the others, and every batch topk_sweep answers None for, take
+# the matrix path.
+TOPK_SWEEP_FNS = ("TransE", "RotatE", "pRotatE", "InterHT")
+
+
+def predict(model, queries, mode: str, k: int = 10, known_triples=None, batch_size: int | None = None):
+    """Link prediction: for each query triple the k best entities in the candidate slot, (h, r, ?) for tail-batch
+    and (?, r, t) for head-batch (the slot's own value is ignored), as (ids [M, k] int64, scores [M, k]) on the
+    model's device: score descending, ties by ascending id, padded with -1 / -inf. With `known_triples`, the
+    answers they already hold for a query are left out (build_exclude). Batches of `batch_size` (1 024) queries run
+    through topk_sweep where it applies and through score_all + topk_rows otherwise (DistMult / ComplEx from the
+    entity planes made once per call). There is no CPU fallback."""
+    k = _check_k(k, "predict")
+    if mode not in ("head-batch", "tail-batch"):
+        raise ValueError("predict: mode must be 'head-batch' or 'tail-batch'")
+    ent = model.entity_embedding
+    ops._need_gpu(ent, model.relation_embedding)
+    dev = ent.device
+    q = queries.detach().cpu().numpy() if isinstance(queries, torch.Tensor) else np.asarray(queries)
+    q = np.ascontiguousarray(q, dtype=np.int64).reshape(-1, 3)
+    M = len(q)
+    bs = int(batch_size or 1024)
+    if bs < 1:
+        raise ValueError("predict: batch_size must be positive")
+    ids = torch.empty((M, k), dtype=torch.int64, device=dev)
+    scores = torch.empty((M, k), dtype=torch.float32, device=dev)
+    ptr = xids = None
+    if known_triples is not None:
+        ptr, xids = build_exclude(q, mode, known_triples)
+    with torch.no_grad():
+        planes = entity_planes(model)  # once per call (DistMult / ComplEx)
+        sweep = model.model_name in TOPK_SWEEP_FNS
+        for s in range(0, M, bs):
+            pos = torch.from_numpy(q[s:s + bs]).to(dev)
+            xp = xi = None
+            nx = 0
+            if ptr is not None:
+                p = ptr[s:s + len(pos) + 1]
+                nx = int(p[-1] - p[0])
+                if nx:
+                    xp = torch.from_numpy(p - p[0]).to(dev)
+                    xi = torch.from_numpy(xids[p[0]:p[-1]]).to(dev)
+            got = topk_sweep(model, pos, mode, k, xp, xi, nx) if sweep else None
+            if got is None:
+                topk_rows(score_all(model, pos, mode, planes=planes), k, xp, xi, ids[s:s + bs], scores[s:s + bs])
+            else:
+                ids[s:s + bs], scores[s:s + bs] = got
+    return ids, scores
+
+
 class RankPipeline:
     """rank_planes over consecutive query batches on two streams: batch i runs its whole chain (query planes,
     kge_eval_rank_planes_phases' pair scores, counting GEMM and finish) on stream i % 2, with a query-plane buffer and
@@ -463,4 +640,4 @@ def test_step(model, test_triples, all_true_triples, args=None, batch_size=None)
 
 
 __all__ = ["build_filter", "score_all", "rank_filtered", "rank_planes", "rank_sweep", "RankPipeline", "metrics_from_ranks", "test_step", "entity_planes",
-           "split_planes", "HEAD_BATCH", "TAIL_BATCH"]
+           "split_planes", "HEAD_BATCH", "TAIL_BATCH", "build_exclude", "topk_sweep", "topk_rows", "predict", "TOPK_MAX"]

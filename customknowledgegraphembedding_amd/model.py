@@ -135,6 +135,13 @@ class _KGEBase(nn.Module):
                                  positive_sample, negative_sample, self._D, self._gamma_f,
                                  self._range_f, rel_off=self._rel_off, modulus=modulus)
 
+    def predict(self, queries, mode, k=10, known_triples=None, batch_size=None):
+        """The k best entities (ids [M, k] int64, scores [M, k]) for each query (h, r, ?) (tail-batch) or (?, r, t)
+        (head-batch), without the answers `known_triples` already hold: evaluate.predict."""
+        from . import evaluate
+
+        return evaluate.predict(self, queries, mode, k=k, known_triples=known_triples, batch_size=batch_size)
+
     def extra_repr(self):
         return (f"model_name={self.model_name}, nentity={self.nentity}, nrelation={self.nrelation}, "
                 f"entity_dim={self.entity_dim}, relation_dim={self.relation_dim}, gamma={self._gamma_f}")
