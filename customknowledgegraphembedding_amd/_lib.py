@@ -231,6 +231,11 @@ SIGNATURES = {
     "kge_sampler_seed": (_c_i, [_c_p, ctypes.c_uint32]),
     "kge_sampler_get": (_c_i, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "kge_sampler_destroy": (None, [_c_p]),
+    "kge_dsampler_table_size": (_c_i64, [_c_i64]),
+    "kge_dsampler_table_build": (_c_i, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64]),
+    # (blob, blob_bytes, idx, B, N, row0, mode, seed, step, step_ptr, pos, neg, neg_ld, weight, stream)
+    "kge_dsampler_sample": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i, ctypes.c_uint64, _c_i64, _c_p,
+                                   _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "kge_transparse_score": (_c_i, [_c_i, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64,
                                     _c_i64, _c_i64, _c_i64, _c_f, _c_p, _c_i64, _c_p, _c_p]),
     "kge_transparse_score_workspace_size": (ctypes.c_size_t, [_c_i, _c_i64, _c_i64, _c_i64]),

@@ -23,8 +23,9 @@ FN_NAMES = {0: "TransE", 1: "DistMult", 2: "ComplEx", 3: "RotatE", 4: "InterHT",
 def parse(path):
     """{mangled name: {field: int}} from the remarks (a kernel compiled in several units appears once)."""
     out, cur = {}, None
-    name_re = re.compile(r"remark: Function Name: (\S+)")
-    field_re = re.compile(r"remark:\s+([A-Za-z][A-Za-z /\[\]]*?):\s+(\d+)")
+    # the remark's text follows "remark: " directly or after the kernel's source position (file:line:column:)
+    name_re = re.compile(r"remark: (?:\S+:\d+:\d+: )?Function Name: (\S+)")
+    field_re = re.compile(r"remark:\s+(?:\S+:\d+:\d+:\s+)?([A-Za-z][A-Za-z /\[\]]*?):\s+(\d+)")
     for line in open(path, errors="replace"):
         m = name_re.search(line)
         if m:
