@@ -1,7 +1,9 @@
 """TranSparse (tensorflow_codes/model.py:96-106,139-142,161-164,187-190,226-235) on the GPU: the MFMA
 forward and the deterministic backward through the C-ABI against the fp64 oracle (torch autograd on
 the same fp32 inputs). Scores: |got - ref| <= 1e-4 * max(1, |ref|). Gradients: |got - ref| <=
-1e-4 * max|ref| per tensor (fp32 sums over up to d * N terms)."""
+1e-4 * max|ref| per tensor (fp32 sums over up to d * N terms). The shapes here are small; real relation
+counts, table sizes, widths past one chunk, row strides and alignments are in test_transparse_shapes_gpu.py
+(cases and the dispatch they aim at: transparse_cases.py)."""
 import numpy as np
 import pytest
 import torch
@@ -10,35 +12,10 @@ from customknowledgegraphembedding_amd import ops
 from customknowledgegraphembedding_amd.model import TFKGEModel
 from oracle import kge_oracle as O
 from tests.conftest import rel_close
+from tests.transparse_cases import _batch, _oracle, _tables
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _tables(E, R, d, seed=0, gamma=12.0):
-    g = torch.Generator().manual_seed(seed)
-    rng = (gamma + 2.0) / d
-    ent = torch.empty(E, d).uniform_(-rng, rng, generator=g)
-    rel = torch.empty(R, d).uniform_(-rng, rng, generator=g)
-    W = torch.empty(R, d, d).uniform_(-rng, rng, generator=g)
-    mask = (torch.empty(R, d, d).uniform_(1, 100, generator=g) >= 50).float()
-    return ent, rel, W, mask
-
-
-def _batch(E, R, B, N, seed=1):
-    g = np.random.RandomState(seed)
-    pos = np.stack([g.randint(E, size=B), g.randint(R, size=B), g.randint(E, size=B)], 1).astype(np.int64)
-    neg = g.randint(E, size=(B, N)).astype(np.int64)
-    return torch.from_numpy(pos), torch.from_numpy(neg)
-
-
-def _oracle(ent, rel, W, mask, pos, neg, mode, gamma, grad=None):
-    t = [x.double().requires_grad_(True) for x in (ent, rel, W)]
-    s = O.transparse_score(t[0], t[1], t[2], mask.double(), pos, neg, mode, gamma)
-    if grad is None:
-        return s.detach().numpy(), None
-    (s * grad.double()).sum().backward()
-    return s.detach().numpy(), [x.grad.numpy() for x in t]
 
 
 CASES = [  # (E, R, d, B, N)
