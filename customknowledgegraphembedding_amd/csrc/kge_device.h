@@ -1924,6 +1924,13 @@ __device__ __forceinline__ float rr_log1p(float e) {
 }
 __device__ __forceinline__ float rr_exp(float x) { return __expf(x); }
 __device__ __forceinline__ float rr_log_sigmoid(float x) { return fminf(x, 0.f) - rr_log1p(__expf(-fabsf(x))); }
+// The fused query pass (QueryGradAcc) takes its softmax / sigmoid weights from the same hardware units (v_exp_f32,
+// v_log_f32, v_rcp_f32): rr_exp, rr_log_sigmoid and this sigmoid. They weight gradient terms only. The log-sigmoid
+// has to be the series form: with log(1 + e) a well-separated row's f = logsigmoid(-s) ~ -e^s flushed to 0 under
+// e^s < 2^-24, dropping the T f half of its weight wa.
+// fsigmoid and rr_log_sigmoid are not sigmoidf and log_sigmoid: those are the libm forms, which the score
+// gradients and every value a caller sees (losses, positive scores) keep. Different functions, different users.
+__device__ __forceinline__ float fsigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
 __device__ __forceinline__ float row_reduce(const float* row, int64_t N, float T, int adversarial, int lane) {
     if (adversarial) {
@@ -2092,60 +2099,13 @@ __global__ __launch_bounds__(kBlock) void step_fwd_kernel(ScoreParams p) {
 //   RED: 0 mean, 1 self-adversarial with the softmax detached, 2 self-adversarial (TF semantics).
 // Scores, the row finish and the per-candidate code are the step forward's (bitwise the same scores).
 // ---------------------------------------------------------------------------------------------
-// InterHT's Jacobian sums on packed fp32 pairs (v_pk_mul / v_pk_fma_f32: two elements per instruction):
-//   x = q0 bh - ah q1 + q2 (tail) or ah q1 - q0 bh + q2 (head), J = -sgn(x) (bh, -ah, 1) resp. (-bh, ah, 1)
-// sgn(x) exactly (0 at x = 0, as tf.abs' gradient) as med3(x 2^127 2^127, -1, 1); the sums take nwa = -wa
-// and nwb = -wb so that nwa sgn(x) = wa Gx. No range mask: past D the candidate, q0, q1 and q2 are 0, so
-// x = 0 and the element adds nothing.
+// sgn on a packed fp32 pair, exactly (0 at x = 0, as tf.abs' gradient): med3(x 2^127 2^127, -1, 1)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 sgn2(f32x2 x) {
     x = x * 0x1p127f;
     x = x * 0x1p127f;
     return f32x2{__builtin_amdgcn_fmed3f(x.x, -1.f, 1.f), __builtin_amdgcn_fmed3f(x.y, -1.f, 1.f)};
 }
-template <bool CH, int V, bool TWO>
-__device__ __forceinline__ void group_jac_ih(const vecf<V>& ca, const vecf<V>& cb, const vecf<V>& q0,
-                                             const vecf<V>& q1, const vecf<V>& q2, float ia, float ib, float nwa,
-                                             float nwb, vecf<V>& a0, vecf<V>& a1, vecf<V>& a2, vecf<V>& b0,
-                                             vecf<V>& b1, vecf<V>& b2) {
-    static_assert(V % 2 == 0, "pairs");
-#pragma unroll
-    for (int i = 0; i < V; i += 2) {
-        const f32x2 ah = f32x2{ca.a[i], ca.a[i + 1]} * ia;
-        const f32x2 bh = f32x2{cb.a[i], cb.a[i + 1]} * ib + 1.f;
-        const f32x2 Q0{q0.a[i], q0.a[i + 1]}, Q1{q1.a[i], q1.a[i + 1]}, Q2{q2.a[i], q2.a[i + 1]};
-        const f32x2 x = CH ? (ah * Q1 - Q0 * bh + Q2) : (Q0 * bh - ah * Q1 + Q2);
-        const f32x2 sg = sgn2(x);
-        auto acc = [&](float nw, vecf<V>& s0, vecf<V>& s1, vecf<V>& s2) {
-            const f32x2 g = sg * nw;  // w Gx
-            f32x2 u0{s0.a[i], s0.a[i + 1]}, u1{s1.a[i], s1.a[i + 1]}, u2{s2.a[i], s2.a[i + 1]};
-            if (CH) {
-                u0 = u0 - g * bh;
-                u1 = u1 + g * ah;
-            } else {
-                u0 = u0 + g * bh;
-                u1 = u1 - g * ah;
-            }
-            u2 = u2 + g;
-            s0.a[i] = u0.x;
-            s0.a[i + 1] = u0.y;
-            s1.a[i] = u1.x;
-            s1.a[i + 1] = u1.y;
-            s2.a[i] = u2.x;
-            s2.a[i + 1] = u2.y;
-        };
-        acc(nwa, a0, a1, a2);
-        if constexpr (TWO) acc(nwb, b0, b1, b2);
-    }
-}
-
-// Softmax / sigmoid weights of the fused query pass on the hardware exp / log / rcp (v_exp_f32, v_log_f32,
-// v_rcp_f32). They weight gradient terms only (the forward's outputs are row_reduce's, in full precision). The
-// log-sigmoid is the row reductions' (rr_log1p's series below 1/128): with log(1 + e) a well-separated row's
-// f = logsigmoid(-s) ~ -e^s flushed to 0 under e^s < 2^-24, dropping the T f half of its weight wa.
-__device__ __forceinline__ float fexp(float x) { return __expf(x); }
-__device__ __forceinline__ float fsigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float flog_sigmoid(float x) { return rr_log_sigmoid(x); }
 
 // (xr, xi) / |(xr, xi)| and 0 at (and, fast form, within FLT_MIN of) the origin: the derivative of RotatE's
 // modulus, in every gradient path. One hardware reciprocal square root for both components
@@ -2157,56 +2117,252 @@ __device__ __forceinline__ void rot_unit(float xr, float xi, float& fr, float& f
     fi = xi * im;
 }
 
-template <int FN, bool CH, int V, bool TWO>
+// ---------------------------------------------------------------------------------------------
+// The gradient of one element's score contribution, per score function: the one definition every backward form
+// reads (cand_grad, group_jac, group_grad, ent_group_term, which only choose what to keep and how to weight it).
+// pRotatE is not in it: its three callers keep their own expression of -g modulus sgn(sin z) cos z, (...) / phase_div
+// and the modulus term |sin z|. Behind this definition their kernels were compiled differently (the libm sin / cos
+// bodies decide whether the G x V element loop unrolls: score_bwd_kernel V4 G8 went from 82 VGPRs to 180 and from
+// 5 waves per SIMD to 2), and pRotatE is outside the fused query pass anyway.
+// An ElemGrad is bound to one column group's query operands; the candidate's halves come per element, as
+// halves() gives them (cand_grad, which needs InterHT's b / |b| by itself, normalises on its own).
+//   residual   the quantity whose modulus the score sums: InterHT x, TransE r, RotatE (xr, xi)
+//   at         what all directions of the element share, under the weight w: G = w d score / d residual
+//   dq         d score / d (q0, q1, q2), term k = c[k] f[k] with c = +-G: a caller adds c f in one expression
+//   dc         d score / d (the candidate's halves; InterHT: the normalised ones), weighted
+// Rounding (-ffp-contract=on fuses per source expression): a product with a sign (+-1, 0) is exact, so the weight
+// may sit on either side of it. The weight is an argument, so that a caller with one weight folds it into the sign
+// first (w sgn, then times the factor, as its code always did) and the two-weight caller passes 1.
+// ---------------------------------------------------------------------------------------------
+template <int FN, bool CH, int V>
+struct ElemGrad {
+    const vecf<V>&q0, &q1, &q2;
+    const bool in;  // the group lies inside the row
+    const ScoreParams& p;
+    static_assert(FN != KGE_PROTATE, "pRotatE's callers keep their own expressions");
+    static constexpr int kNQ = FN == KGE_INTERHT ? 3 : ((FN == KGE_COMPLEX || FN == KGE_ROTATE) ? 2 : 1);
+    static constexpr bool kPairs = FN == KGE_INTERHT && V % 2 == 0;  // jac_pairs exists
+    struct At {
+        float G, ur, ui;  // ur, ui: RotatE's rot_unit of the residual
+    };
+
+    __device__ __forceinline__ static void halves(const vecf<V>& ca, const vecf<V>& cb, int i, float ia, float ib,
+                                                  float& a, float& b) {
+        if constexpr (FN == KGE_INTERHT) {
+            a = ca.a[i] * ia;
+            b = cb.a[i] * ib + 1.f;
+        } else {
+            a = ca.a[i];
+            b = cb.a[i];
+        }
+    }
+
+    // T: float, or a packed pair (InterHT). xi is RotatE's second component. DistMult and ComplEx are bilinear.
+    template <class T>
+    __device__ __forceinline__ T residual(T a, T b, T Q0, T Q1, T Q2, T& xi) const {
+        if constexpr (FN == KGE_INTERHT) {
+            return CH ? (a * Q1 - Q0 * b + Q2) : (Q0 * b - a * Q1 + Q2);
+        } else if constexpr (FN == KGE_TRANSE) {
+            return CH ? (a + Q0) : (Q0 - a);
+        } else if constexpr (FN == KGE_ROTATE) {
+            xi = Q1 - b;
+            return Q0 - a;
+        } else {
+            return a;
+        }
+    }
+
+    // nsg: InterHT's -sgn(x) of this group where the forward kept it (cand_score_with)
+    __device__ __forceinline__ At at(int i, float a, float b, float w, const vecf<V>* nsg = nullptr) const {
+        At t{w, 0.f, 0.f};
+        float xi;
+        if constexpr (FN == KGE_INTERHT) {
+            t.G = nsg ? w * nsg->a[i] : (in ? -w * sgnf(residual(a, b, q0.a[i], q1.a[i], q2.a[i], xi)) : 0.f);
+        } else if constexpr (FN == KGE_TRANSE) {
+            t.G = -w * sgnf(residual(a, b, q0.a[i], q1.a[i], q2.a[i], xi));
+        } else if constexpr (FN == KGE_ROTATE) {
+            const float xr = residual(a, b, q0.a[i], q1.a[i], q2.a[i], xi);
+            rot_unit(xr, xi, t.ur, t.ui);
+            t.G = -w;
+        }
+        return t;
+    }
+
+    // T: float, or a packed pair (InterHT's jac_pairs)
+    template <class T>
+    __device__ __forceinline__ static void dq_terms(T G, T a, T b, T ur, T ui, T (&c)[3], T (&f)[3]) {
+        const T zero = 0.f, one = 1.f;
+        c[0] = G;
+        c[1] = kNQ > 1 ? G : zero;  // 0 0: an operand the function does not have
+        c[2] = kNQ > 2 ? G : zero;
+        f[0] = f[1] = f[2] = zero;
+        if constexpr (FN == KGE_INTERHT) {
+            c[CH ? 0 : 1] = -G;
+            f[0] = b;
+            f[1] = a;
+            f[2] = one;
+        } else if constexpr (FN == KGE_ROTATE) {
+            f[0] = ur;
+            f[1] = ui;
+        } else if constexpr (FN == KGE_TRANSE) {
+            f[0] = one;
+        } else {
+            f[0] = a;
+            if constexpr (FN == KGE_COMPLEX) f[1] = b;
+        }
+    }
+    __device__ __forceinline__ void dq(const At& t, float a, float b, float (&c)[3], float (&f)[3]) const {
+        dq_terms(t.G, a, b, t.ur, t.ui, c, f);
+    }
+
+    __device__ __forceinline__ void dc(const At& t, int i, float& da, float& db) const {
+        if constexpr (FN == KGE_INTERHT) {
+            da = (CH ? t.G : -t.G) * q1.a[i];
+            db = (CH ? -t.G : t.G) * q0.a[i];
+        } else if constexpr (FN == KGE_TRANSE) {
+            da = CH ? t.G : -t.G;
+        } else if constexpr (FN == KGE_DISTMULT) {
+            da = t.G * q0.a[i];
+        } else if constexpr (FN == KGE_COMPLEX) {
+            da = t.G * q0.a[i];
+            db = t.G * q1.a[i];
+        } else if constexpr (FN == KGE_ROTATE) {
+            da = -t.G * t.ur;
+            db = -t.G * t.ui;
+        }
+    }
+
+    // d_k += term k: one fused multiply-add per operand the function has
+    __device__ __forceinline__ void add_dq(const At& t, float a, float b, float& d0, float& d1, float& d2) const {
+        float c[3], f[3];
+        dq(t, a, b, c, f);
+        d0 += c[0] * f[0];
+        if constexpr (kNQ > 1) d1 += c[1] * f[1];
+        if constexpr (kNQ > 2) d2 += c[2] * f[2];
+    }
+
+    // InterHT's Jacobian sums on packed fp32 pairs (v_pk_mul / v_pk_fma_f32: two elements per instruction), a
+    // measured optimisation of the fused forward: the sign by sgn2, and the sums take nwa = -wa and nwb = -wb so
+    // that nwa sgn(x) = wa G. No range mask: past D the candidate, q0, q1 and q2 are 0, so x = 0 and the element
+    // adds nothing.
+    template <bool TWO>
+    __device__ __forceinline__ void jac_pairs(const vecf<V>& ca, const vecf<V>& cb, float ia, float ib, float nwa,
+                                              float nwb, vecf<V>& a0, vecf<V>& a1, vecf<V>& a2, vecf<V>& b0,
+                                              vecf<V>& b1, vecf<V>& b2) const {
+        static_assert(kPairs, "InterHT at an even width");
+#pragma unroll
+        for (int i = 0; i < V; i += 2) {
+            const f32x2 ah = f32x2{ca.a[i], ca.a[i + 1]} * ia;
+            const f32x2 bh = f32x2{cb.a[i], cb.a[i + 1]} * ib + 1.f;
+            const f32x2 Q0{q0.a[i], q0.a[i + 1]}, Q1{q1.a[i], q1.a[i + 1]}, Q2{q2.a[i], q2.a[i + 1]};
+            f32x2 xi;
+            const f32x2 sg = sgn2(residual(ah, bh, Q0, Q1, Q2, xi));
+            auto acc = [&](float nw, vecf<V>& s0, vecf<V>& s1, vecf<V>& s2) {
+                f32x2 c[3], f[3];
+                dq_terms(sg * nw, ah, bh, xi, xi, c, f);  // sg nw = w G
+                f32x2 u0{s0.a[i], s0.a[i + 1]}, u1{s1.a[i], s1.a[i + 1]}, u2{s2.a[i], s2.a[i + 1]};
+                u0 = u0 + c[0] * f[0];
+                u1 = u1 + c[1] * f[1];
+                u2 = u2 + c[2] * f[2];
+                s0.a[i] = u0.x;
+                s0.a[i + 1] = u0.y;
+                s1.a[i] = u1.x;
+                s1.a[i + 1] = u1.y;
+                s2.a[i] = u2.x;
+                s2.a[i + 1] = u2.y;
+            };
+            acc(nwa, a0, a1, a2);
+            if constexpr (TWO) acc(nwb, b0, b1, b2);
+        }
+    }
+};
+
+// The fused query pass's sums of one column group: A += wa J and, TWO, B += wb J, with J = d score / d (q0, q1, q2).
+// PAIRS: take the packed form where the definition has one.
+template <int FN, bool CH, int V, bool TWO, bool PAIRS = false>
 __device__ __forceinline__ void group_jac(const vecf<V>& ca, const vecf<V>& cb, const vecf<V>& q0, const vecf<V>& q1,
                                           const vecf<V>& q2, bool in, float ia, float ib, const ScoreParams& p,
                                           float wa, float wb, vecf<V>& a0, vecf<V>& a1, vecf<V>& a2, vecf<V>& b0,
                                           vecf<V>& b1, vecf<V>& b2, const vecf<V>* nsg = nullptr) {
+    const ElemGrad<FN, CH, V> e{q0, q1, q2, in, p};
+    if constexpr (PAIRS && ElemGrad<FN, CH, V>::kPairs) {
+        e.template jac_pairs<TWO>(ca, cb, ia, ib, -wa, -wb, a0, a1, a2, b0, b1, b2);
+    } else {
 #pragma unroll
-    for (int i = 0; i < V; ++i) {
-        const float x = ca.a[i];
-        float j0 = 0.f, j1 = 0.f, j2 = 0.f;  // d score / d (q0, q1, q2) of this element
-        if constexpr (FN == KGE_INTERHT) {
-            const float ah = x * ia;
-            const float bh = cb.a[i] * ib + 1.f;
-            if (CH) {
-                const float xx = nsg ? 0.f : ah * q1.a[i] - q0.a[i] * bh + q2.a[i];
-                const float Gx = nsg ? nsg->a[i] : (in ? -sgnf(xx) : 0.f);
-                j1 = Gx * ah;
-                j0 = -Gx * bh;
-                j2 = Gx;
-            } else {
-                const float xx = nsg ? 0.f : q0.a[i] * bh - ah * q1.a[i] + q2.a[i];
-                const float Gx = nsg ? nsg->a[i] : (in ? -sgnf(xx) : 0.f);
-                j0 = Gx * bh;
-                j1 = -Gx * ah;
-                j2 = Gx;
+        for (int i = 0; i < V; ++i) {
+            float a, b, c[3], f[3];
+            e.halves(ca, cb, i, ia, ib, a, b);
+            e.dq(e.at(i, a, b, 1.f, nsg), a, b, c, f);
+            const float j0 = c[0] * f[0], j1 = c[1] * f[1], j2 = c[2] * f[2];  // the unit direction
+            a0.a[i] += wa * j0;
+            a1.a[i] += wa * j1;
+            a2.a[i] += wa * j2;
+            if constexpr (TWO) {
+                b0.a[i] += wb * j0;
+                b1.a[i] += wb * j1;
+                b2.a[i] += wb * j2;
             }
-        } else if constexpr (FN == KGE_TRANSE) {
-            const float r = CH ? (x + q0.a[i]) : (q0.a[i] - x);
-            j0 = -sgnf(r);
-        } else if constexpr (FN == KGE_DISTMULT) {
-            j0 = x;
-        } else if constexpr (FN == KGE_COMPLEX) {
-            j0 = x;
-            j1 = cb.a[i];
-        } else if constexpr (FN == KGE_ROTATE) {
-            const float xr = q0.a[i] - x, xi = q1.a[i] - cb.a[i];
-            float fr, fi;
-            rot_unit(xr, xi, fr, fi);
-            j0 = -fr;
-            j1 = -fi;
-        }
-        a0.a[i] += wa * j0;
-        a1.a[i] += wa * j1;
-        a2.a[i] += wa * j2;
-        if constexpr (TWO) {
-            b0.a[i] += wb * j0;
-            b1.a[i] += wb * j1;
-            b2.a[i] += wb * j2;
         }
     }
 }
+
+// The fused query pass's running state of one wave (step_fwd_grad_kernel, shard_fwd_grad_kernel): the sums A and B
+// over the candidates seen so far and the online softmax's (m, Z, Ln), all relative to the running maximum m, and
+// the per-candidate update. The state is bound by reference to the kernel's own locals: held by value in one object,
+// its (m, Z, Ln) part stayed in memory in the shard kernel (3 floats per lane, promoted to LDS).
+template <int FN, bool CH, int V, int G, int RED>
+struct QueryGradAcc {
+    static constexpr bool TWO = RED == 2;
+    vecf<V> (&a0)[G], (&a1)[G], (&a2)[G], (&b0)[G], (&b1)[G], (&b2)[G];
+    float &mrun, &Z, &Ln;
+
+    // one candidate's contribution (s is wave-uniform; nst: InterHT's half-norms); T: the softmax temperature.
+    // nsg: InterHT's signs where the forward kept them (cand_score_with); no kernel keeps them at present, so every
+    // caller leaves it null.
+    template <bool PAIRS>
+    __device__ __forceinline__ void add(const Cand<FN, V, G>& c, const LdsQuery<V>& q, float s, float2 nst, float T,
+                                        int lane, int DV, const ScoreParams& p, const vecf<V>* nsg = nullptr) {
+        float wa, wb = 0.f;
+        if constexpr (RED == 0) {
+            wa = -fsigmoid(s);
+        } else {
+            const float t = T * s;
+            if (t > mrun) {  // online softmax: rescale the running sums to the new maximum
+                const float sc = rr_exp(mrun - t);
+                Z *= sc;
+                Ln *= sc;
+#pragma unroll
+                for (int k = 0; k < G; ++k)
+#pragma unroll
+                    for (int i = 0; i < V; ++i) {
+                        a0[k].a[i] *= sc;
+                        a1[k].a[i] *= sc;
+                        a2[k].a[i] *= sc;
+                        if constexpr (TWO) {
+                            b0[k].a[i] *= sc;
+                            b1[k].a[i] *= sc;
+                            b2[k].a[i] *= sc;
+                        }
+                    }
+                mrun = t;
+            }
+            const float e = rr_exp(t - mrun);
+            const float f = rr_log_sigmoid(-s);
+            Z += e;
+            Ln += e * f;
+            wa = e * -fsigmoid(s);
+            if constexpr (TWO) {
+                wa += e * (T * f);
+                wb = e;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+            group_jac<FN, CH, V, TWO, PAIRS>(c.ca[k], c.cb[k], q.q0[k], q.q1[k], q.q2[k], (lane + k * kWave) < DV,
+                                             nst.x, nst.y, p, wa, wb, a0[k], a1[k], a2[k], b0[k], b1[k], b2[k],
+                                             nsg ? nsg + k : nullptr);
+    }
+};
 
 template <int FN, bool CH, int V, int G, int RED>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) void step_fwd_grad_kernel(ScoreParams p) {
@@ -2244,60 +2400,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
 #pragma unroll
     for (int k = 0; k < G; ++k) a0[k] = a1[k] = a2[k] = b0[k] = b1[k] = b2[k] = vzero<V>();
     float mrun = -INFINITY, Z = 0.f, Ln = 0.f;
+    QueryGradAcc<FN, CH, V, G, RED> qg{a0, a1, a2, b0, b1, b2, mrun, Z, Ln};
     {
-
-        // one candidate's contribution (s is wave-uniform)
-        auto accumulate = [&](const Cand<FN, V, G>& c, const LdsQuery<V>& q, float s, float2 nst,
-                              const vecf<V>* nsg) {
-            auto xexp = [](float x) { return fexp(x); };
-            auto xsig = [](float x) { return fsigmoid(x); };
-            auto xlogsig = [](float x) { return flog_sigmoid(x); };
-            float wa, wb = 0.f;
-            if constexpr (RED == 0) {
-                wa = -xsig(s);
-            } else {
-                const float t = T * s;
-                if (t > mrun) {  // online softmax: rescale the running sums to the new maximum
-                    const float sc = xexp(mrun - t);
-                    Z *= sc;
-                    Ln *= sc;
-#pragma unroll
-                    for (int k = 0; k < G; ++k)
-#pragma unroll
-                        for (int i = 0; i < V; ++i) {
-                            a0[k].a[i] *= sc;
-                            a1[k].a[i] *= sc;
-                            a2[k].a[i] *= sc;
-                            if constexpr (TWO) {
-                                b0[k].a[i] *= sc;
-                                b1[k].a[i] *= sc;
-                                b2[k].a[i] *= sc;
-                            }
-                        }
-                    mrun = t;
-                }
-                const float e = xexp(t - mrun);
-                const float f = xlogsig(-s);
-                Z += e;
-                Ln += e * f;
-                wa = e * -xsig(s);
-                if constexpr (TWO) {
-                    wa += e * (T * f);
-                    wb = e;
-                }
-            }
-            if constexpr (FN == KGE_INTERHT && V % 2 == 0) {
-#pragma unroll
-                for (int k = 0; k < G; ++k)
-                    group_jac_ih<CH, V, TWO>(c.ca[k], c.cb[k], q.q0[k], q.q1[k], q.q2[k], nst.x, nst.y, -wa, -wb, a0[k],
-                                             a1[k], a2[k], b0[k], b1[k], b2[k]);
-                return;
-            }
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                group_jac<FN, CH, V, TWO>(c.ca[k], c.cb[k], q.q0[k], q.q1[k], q.q2[k], (lane + k * kWave) < DV, nst.x,
-                                          nst.y, p, wa, wb, a0[k], a1[k], a2[k], b0[k], b1[k], b2[k], nsg ? nsg + k : nullptr);
-        };
         const int64_t per = (p.N + kWavesPerBlock - 1) / kWavesPerBlock;
         const int64_t lo = w * per, hi = min(p.N, lo + per);
         for (int64_t c0 = lo; c0 < hi; c0 += kWave) {
@@ -2336,7 +2440,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
                 // opaque copies of the half-norms: the gradient recomputes the candidate's terms
                 // instead of keeping the score's per-element values alive across the reductions
                 asm volatile("" : "+v"(nst.x), "+v"(nst.y));
-                accumulate(c, q, s, nst, nullptr);
+                qg.template add<true>(c, q, s, nst, T, lane, DV, p);
             };
             // software pipeline (as score_run): row j + 1 is in flight while row j is reduced
             x0.load(cand_row(p, readlane64(my_id, 0), ok0), ok0, p.D, lane);
@@ -2467,31 +2571,12 @@ __device__ __forceinline__ void cand_grad(const Cand<FN, V, G>& c, const Query<F
                 const float ah = c.ca[k].a[i] * ia;
                 const float bn = c.cb[k].a[i] * ib;
                 const float bh = bn + 1.f;
-                const float q0 = q.q0[k].a[i], q1 = q.q1[k].a[i], q2 = q.q2[k].a[i];
-                const bool in = (lane + k * kWave) < DV;
-                float dah, dbn;
-                if (CH) {  // x = a_head * b_tail - a_tail * b_head + re_mid, candidate = head
-                    const float x = ah * q1 - q0 * bh + q2;
-                    const float Gx = in ? -g * sgnf(x) : 0.f;
-                    dah = Gx * q1;
-                    dbn = -Gx * q0;
-                    if (ACC_Q) {
-                        dq1[k].a[i] += Gx * ah;
-                        dq0[k].a[i] += -Gx * bh;
-                        dq2[k].a[i] += Gx;
-                    }
-                } else {
-                    const float x = q0 * bh - ah * q1 + q2;
-                    const float Gx = in ? -g * sgnf(x) : 0.f;
-                    dah = -Gx * q1;
-                    dbn = Gx * q0;
-                    if (ACC_Q) {
-                        dq0[k].a[i] += Gx * bh;
-                        dq1[k].a[i] += -Gx * ah;
-                        dq2[k].a[i] += Gx;
-                    }
-                }
+                const ElemGrad<FN, CH, V> e{q.q0[k], q.q1[k], q.q2[k], (lane + k * kWave) < DV, p};
+                const auto t = e.at(i, ah, bh, g);
+                if (ACC_Q) e.add_dq(t, ah, bh, dq0[k].a[i], dq1[k].a[i], dq2[k].a[i]);
                 if (WANT_C) {
+                    float dah, dbn;
+                    e.dc(t, i, dah, dbn);
                     dca[k].a[i] = dah;
                     dcb[k].a[i] = dbn;
                     dota += ah * dah;
@@ -2512,7 +2597,7 @@ __device__ __forceinline__ void cand_grad(const Cand<FN, V, G>& c, const Query<F
                     dcb[k].a[i] = (dcb[k].a[i] - bn * dotb) * ib;
                 }
         }
-    } else {
+    } else if constexpr (FN == KGE_PROTATE) {  // not an ElemGrad caller: see there
         float ysum = 0.f;
 #pragma unroll
         for (int k = 0; k < G; ++k)
@@ -2520,51 +2605,36 @@ __device__ __forceinline__ void cand_grad(const Cand<FN, V, G>& c, const Query<F
             for (int i = 0; i < V; ++i) {
                 const float x = c.ca[k].a[i];
                 const bool in = (lane + k * kWave) < DV;
-                float da = 0.f, db = 0.f;
-                if constexpr (FN == KGE_TRANSE) {
-                    const float r = CH ? (x + q.q0[k].a[i]) : (q.q0[k].a[i] - x);
-                    const float Gx = -g * sgnf(r);  // dL/d(residual)
-                    da = CH ? Gx : -Gx;
-                    if (ACC_Q) dq0[k].a[i] += Gx;
-                } else if constexpr (FN == KGE_DISTMULT) {
-                    da = g * q.q0[k].a[i];
-                    if (ACC_Q) dq0[k].a[i] += g * x;
-                } else if constexpr (FN == KGE_COMPLEX) {
-                    const float y = c.cb[k].a[i];
-                    da = g * q.q0[k].a[i];
-                    db = g * q.q1[k].a[i];
-                    if (ACC_Q) {
-                        dq0[k].a[i] += g * x;
-                        dq1[k].a[i] += g * y;
-                    }
-                } else if constexpr (FN == KGE_ROTATE) {
-                    const float y = c.cb[k].a[i];
-                    const float xr = q.q0[k].a[i] - x, xi = q.q1[k].a[i] - y;
-                    float fr, fi;
-                    rot_unit(xr, xi, fr, fi);
-                    da = g * fr;
-                    db = g * fi;
-                    if (ACC_Q) {
-                        dq0[k].a[i] += -g * fr;
-                        dq1[k].a[i] += -g * fi;
-                    }
-                } else if constexpr (FN == KGE_PROTATE) {
-                    const float pc = x / p.phase_div;
-                    const float z = CH ? (pc + q.q0[k].a[i]) : (q.q0[k].a[i] - pc);
-                    const float sz = sinf(z);
-                    const float Gx = in ? -g * p.modulus * sgnf(sz) * cosf(z) : 0.f;
-                    da = (CH ? Gx : -Gx) / p.phase_div;
-                    if (ACC_Q) dq0[k].a[i] += Gx;
-                    ysum += in ? fabsf(sz) : 0.f;
-                }
+                const float pc = x / p.phase_div;
+                const float z = CH ? (pc + q.q0[k].a[i]) : (q.q0[k].a[i] - pc);
+                const float sz = sinf(z);
+                const float Gx = in ? -g * p.modulus * sgnf(sz) * cosf(z) : 0.f;
+                const float da = (CH ? Gx : -Gx) / p.phase_div;
+                if (ACC_Q) dq0[k].a[i] += Gx;
+                ysum += in ? fabsf(sz) : 0.f;
                 if (WANT_C) {
+                    dca[k].a[i] = in ? da : 0.f;
+                    dcb[k].a[i] = 0.f;
+                }
+            }
+        if (ACC_Q) dmod += -g * wave_sum(ysum);
+    } else {
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const float x = c.ca[k].a[i], y = c.cb[k].a[i];
+                const bool in = (lane + k * kWave) < DV;
+                const ElemGrad<FN, CH, V> e{q.q0[k], q.q1[k], q.q2[k], in, p};
+                const auto t = e.at(i, x, y, g);
+                if (ACC_Q) e.add_dq(t, x, y, dq0[k].a[i], dq1[k].a[i], dq2[k].a[i]);
+                if (WANT_C) {
+                    float da = 0.f, db = 0.f;
+                    e.dc(t, i, da, db);
                     dca[k].a[i] = in ? da : 0.f;
                     dcb[k].a[i] = in ? db : 0.f;
                 }
             }
-        if constexpr (FN == KGE_PROTATE) {
-            if (ACC_Q) dmod += -g * wave_sum(ysum);
-        }
     }
 }
 
@@ -3034,45 +3104,22 @@ __device__ __forceinline__ void group_grad(const vecf<V>& ca, const vecf<V>& cb,
                                            const vecf<V>& q2, bool in, float g, float ia, float ib,
                                            const ScoreParams& p, vecf<V>& dq0, vecf<V>& dq1, vecf<V>& dq2,
                                            float& dmod) {
+    if constexpr (FN == KGE_PROTATE) {  // not an ElemGrad caller: see there
 #pragma unroll
-    for (int i = 0; i < V; ++i) {
-        const float x = ca.a[i];
-        if constexpr (FN == KGE_INTERHT) {
-            const float ah = x * ia;
-            const float bh = cb.a[i] * ib + 1.f;
-            if (CH) {
-                const float xx = ah * q1.a[i] - q0.a[i] * bh + q2.a[i];
-                const float Gx = in ? -g * sgnf(xx) : 0.f;
-                dq1.a[i] += Gx * ah;
-                dq0.a[i] += -Gx * bh;
-                dq2.a[i] += Gx;
-            } else {
-                const float xx = q0.a[i] * bh - ah * q1.a[i] + q2.a[i];
-                const float Gx = in ? -g * sgnf(xx) : 0.f;
-                dq0.a[i] += Gx * bh;
-                dq1.a[i] += -Gx * ah;
-                dq2.a[i] += Gx;
-            }
-        } else if constexpr (FN == KGE_TRANSE) {
-            const float r = CH ? (x + q0.a[i]) : (q0.a[i] - x);
-            dq0.a[i] += -g * sgnf(r);
-        } else if constexpr (FN == KGE_DISTMULT) {
-            dq0.a[i] += g * x;
-        } else if constexpr (FN == KGE_COMPLEX) {
-            dq0.a[i] += g * x;
-            dq1.a[i] += g * cb.a[i];
-        } else if constexpr (FN == KGE_ROTATE) {
-            const float xr = q0.a[i] - x, xi = q1.a[i] - cb.a[i];
-            float fr, fi;
-            rot_unit(xr, xi, fr, fi);
-            dq0.a[i] += -g * fr;
-            dq1.a[i] += -g * fi;
-        } else if constexpr (FN == KGE_PROTATE) {
-            const float pc = x / p.phase_div;
+        for (int i = 0; i < V; ++i) {
+            const float pc = ca.a[i] / p.phase_div;
             const float z = CH ? (pc + q0.a[i]) : (q0.a[i] - pc);
             const float sz = sinf(z);
             dq0.a[i] += in ? -g * p.modulus * sgnf(sz) * cosf(z) : 0.f;
             dmod += in ? -g * fabsf(sz) : 0.f;
+        }
+    } else {
+        const ElemGrad<FN, CH, V> e{q0, q1, q2, in, p};
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            float a, b;
+            e.halves(ca, cb, i, ia, ib, a, b);
+            e.add_dq(e.at(i, a, b, g), a, b, dq0.a[i], dq1.a[i], dq2.a[i]);
         }
     }
 }
@@ -3418,47 +3465,26 @@ template <int FN, bool CH, int V>
 __device__ __forceinline__ void ent_group_term(const vecf<V>& ca, const vecf<V>& cb, const vecf<V>& q0,
                                                const vecf<V>& q1, const vecf<V>& q2, bool in, float g, float ia,
                                                float ib, const ScoreParams& p, vecf<V>& sa, vecf<V>& sb) {
+    if constexpr (FN == KGE_PROTATE) {  // not an ElemGrad caller: see there
 #pragma unroll
-    for (int i = 0; i < V; ++i) {
-        const float x = ca.a[i];
-        float da = 0.f, db = 0.f;
-        if constexpr (FN == KGE_INTERHT) {  // normalised-space terms (dy of d(x/n))
-            const float ah = x * ia;
-            const float bh = cb.a[i] * ib + 1.f;
-            if (CH) {
-                const float xx = ah * q1.a[i] - q0.a[i] * bh + q2.a[i];
-                const float Gx = in ? -g * sgnf(xx) : 0.f;
-                da = Gx * q1.a[i];
-                db = -Gx * q0.a[i];
-            } else {
-                const float xx = q0.a[i] * bh - ah * q1.a[i] + q2.a[i];
-                const float Gx = in ? -g * sgnf(xx) : 0.f;
-                da = -Gx * q1.a[i];
-                db = Gx * q0.a[i];
-            }
-        } else if constexpr (FN == KGE_TRANSE) {
-            const float r = CH ? (x + q0.a[i]) : (q0.a[i] - x);
-            const float Gx = -g * sgnf(r);
-            da = CH ? Gx : -Gx;
-        } else if constexpr (FN == KGE_DISTMULT) {
-            da = g * q0.a[i];
-        } else if constexpr (FN == KGE_COMPLEX) {
-            da = g * q0.a[i];
-            db = g * q1.a[i];
-        } else if constexpr (FN == KGE_ROTATE) {
-            const float xr = q0.a[i] - x, xi = q1.a[i] - cb.a[i];
-            float fr, fi;
-            rot_unit(xr, xi, fr, fi);
-            da = g * fr;
-            db = g * fi;
-        } else if constexpr (FN == KGE_PROTATE) {
-            const float pc = x / p.phase_div;
+        for (int i = 0; i < V; ++i) {
+            const float pc = ca.a[i] / p.phase_div;
             const float z = CH ? (pc + q0.a[i]) : (q0.a[i] - pc);
             const float Gx = in ? -g * p.modulus * sgnf(sinf(z)) * cosf(z) : 0.f;
-            da = (CH ? Gx : -Gx) / p.phase_div;
+            const float da = (CH ? Gx : -Gx) / p.phase_div, db = 0.f;
+            sa.a[i] += in ? da : 0.f;
+            sb.a[i] += in ? db : 0.f;
         }
-        sa.a[i] += in ? da : 0.f;
-        sb.a[i] += in ? db : 0.f;
+    } else {
+        const ElemGrad<FN, CH, V> e{q0, q1, q2, in, p};
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            float a, b, da = 0.f, db = 0.f;  // InterHT: the normalised-space terms (dy of d(x/n))
+            e.halves(ca, cb, i, ia, ib, a, b);
+            e.dc(e.at(i, a, b, g), i, da, db);
+            sa.a[i] += in ? da : 0.f;
+            sb.a[i] += in ? db : 0.f;
+        }
     }
 }
 

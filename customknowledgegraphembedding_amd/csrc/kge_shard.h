@@ -1,6 +1,6 @@
 // kge_shard.h — device kernels of the ROW-SHARDED train step (owner-computes).
 // Included by kge_device.h ahead of its dispatch section; builds on its templates (Query, Cand,
-// cand_score, group_jac, cand_grad, rows_finalize, for_owned_runs).
+// cand_score, QueryGradAcc, cand_grad, rows_finalize, for_owned_runs).
 //
 // W ranks each hold the entity rows [c_base, c_base + c_rows) of one table, the replicated relation
 // table, the same global batch (B = W * home_B rows; home rank h's replica batch is rows
@@ -101,53 +101,17 @@ __global__ __launch_bounds__(kBlock) void shard_fwd_grad_kernel(ScoreParams p) {
 #pragma unroll
     for (int k = 0; k < G; ++k) a0[k] = a1[k] = a2[k] = b0[k] = b1[k] = b2[k] = vzero<V>();
     float mrun = -INFINITY, Z = 0.f, Ln = 0.f;
+    QueryGradAcc<FN, CH, V, G, RED> qg{a0, a1, a2, b0, b1, b2, mrun, Z, Ln};
     {
+        // the weights on the hardware exp / log / rcp, as the single-GPU fused forward (the merged stats stay within
+        // fp32 rounding of the libm ones); the scalar Jacobian form at every width; the mean's (Z, Ln) are this
+        // kernel's own: the count and the sum of f
         auto accumulate = [&](const Cand<FN, V, G>& c, const LdsQuery<V>& q, float s, float2 nst) {
-            // the hardware exp / log / rcp, as the single-GPU fused forward (per candidate these were most of
-            // a DistMult wave's VALU work); the merged stats stay within fp32 rounding of the libm ones
-            auto expf = [](float x) { return fexp(x); };
-            auto sigmoidf = [](float x) { return fsigmoid(x); };
-            auto log_sigmoid = [](float x) { return flog_sigmoid(x); };
-            float wa, wb = 0.f;
             if constexpr (RED == 0) {
-                wa = -sigmoidf(s);
                 Z += 1.f;
-                Ln += log_sigmoid(-s);
-            } else {
-                const float t = T * s;
-                if (t > mrun) {  // online softmax: rescale the running sums to the new maximum
-                    const float sc = expf(mrun - t);
-                    Z *= sc;
-                    Ln *= sc;
-#pragma unroll
-                    for (int k = 0; k < G; ++k)
-#pragma unroll
-                        for (int i = 0; i < V; ++i) {
-                            a0[k].a[i] *= sc;
-                            a1[k].a[i] *= sc;
-                            a2[k].a[i] *= sc;
-                            if constexpr (TWO) {
-                                b0[k].a[i] *= sc;
-                                b1[k].a[i] *= sc;
-                                b2[k].a[i] *= sc;
-                            }
-                        }
-                    mrun = t;
-                }
-                const float e = expf(t - mrun);
-                const float f = log_sigmoid(-s);
-                Z += e;
-                Ln += e * f;
-                wa = e * -sigmoidf(s);
-                if constexpr (TWO) {
-                    wa += e * (T * f);
-                    wb = e;
-                }
+                Ln += rr_log_sigmoid(-s);
             }
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                group_jac<FN, CH, V, TWO>(c.ca[k], c.cb[k], q.q0[k], q.q1[k], q.q2[k], (lane + k * kWave) < DV, nst.x,
-                                          nst.y, p, wa, wb, a0[k], a1[k], a2[k], b0[k], b1[k], b2[k]);
+            qg.template add<false>(c, q, s, nst, T, lane, DV, p);
         };
         const int64_t per = (p.N + kWavesPerBlock - 1) / kWavesPerBlock;
         const int64_t lo = w * per, hi = min(p.N, lo + per);
