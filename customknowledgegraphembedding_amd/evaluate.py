@@ -6,7 +6,8 @@ the positive with bias -1; ranks come from argsort). BASELINE config C5.
 The scores of a query batch against all E entities are computed on the GPU:
   * DistMult / ComplEx: S = Q . E^T at fp32 accuracy on the bf16 matrix cores (kge_eval_query +
     kge_gemm_nt_bf16x3: bf16x3 split in registers, six products, fp32 accumulation);
-  * every other score function: the fused VALU scorer with candidate ids 0..E-1 (row stride 0).
+  * every other score function, and a DistMult / ComplEx table without planes whose rows take no float4 loads:
+    the fused VALU scorer with candidate ids 0..E-1 (row stride 0).
 Ranks are exact integers from kge_rank_filtered: rank = 1 + #(unfiltered e != truth with
 s_e > s_truth). Ties count in the positive's favour; upstream's unstable argsort leaves them
 arbitrary, which no test here exercises (continuous random scores). test_step ranks DistMult / ComplEx batches
@@ -75,7 +76,8 @@ def entity_planes(model) -> torch.Tensor | None:
     """The entity table's bf16 planes for one evaluation pass (DistMult / ComplEx), made once and passed to
     every score_all call of the pass: the table does not change while it is evaluated. None for the other
     score functions, and None where the planes do not fit (PLANES_MAX_BYTES, or no device memory for their
-    1.5x the table): score_all then splits the operands at staging (kge_gemm_nt_bf16x3), at the same accuracy."""
+    1.5x the table): score_all then splits the operands at staging (kge_gemm_nt_bf16x3), at the same accuracy, or,
+    where the table's rows take no float4 loads, scores through the fused scorer."""
     if model.model_name not in MFMA_FNS:
         return None
     ent = model.entity_embedding.detach()
@@ -90,11 +92,19 @@ def entity_planes(model) -> torch.Tensor | None:
 _Q_PLANES = {}
 
 
+def _float4_rows(*tables) -> bool:
+    """Whether every row of every table starts on a 16-B boundary: the base 16-B aligned and the row stride a
+    multiple of 4 floats (what kge_eval_query_planes and kge_gemm_nt_bf16x3 need of their operands)."""
+    return all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 for t in tables)
+
+
 def score_all(model, positive_sample: torch.Tensor, mode: str, out: torch.Tensor | None = None,
               planes: torch.Tensor | None = None) -> torch.Tensor:
     """[B, E] scores of every entity as the candidate (head-batch or tail-batch). DistMult / ComplEx: pass
     `planes` = entity_planes(model), made once per evaluation pass (without it the call splits the table
-    itself: kge_gemm_nt_bf16x3, the operands split at staging)."""
+    itself: kge_gemm_nt_bf16x3, the operands split at staging; or, where K, the table's row stride or its base
+    is off 16 B, scores every entity through the fused scorer, as for the distance models: any table
+    kge_score_indexed accepts)."""
     m = ops.mode_id(mode)
     ent, rel = model.entity_embedding.detach(), model.relation_embedding.detach()
     B, E = positive_sample.shape[0], ent.shape[0]
@@ -120,7 +130,7 @@ def score_all(model, positive_sample: torch.Tensor, mode: str, out: torch.Tensor
         # S = Q . E^T at fp32 accuracy on the bf16 matrix cores (bf16x3 terms, six products): from the pass's
         # entity planes and the batch's query planes (kge_eval_query_planes: the query rows written as planes, one
         # launch), or with the operands split at staging
-        if planes is not None and model._D % 4 == 0 and ent.data_ptr() % 16 == 0 and rel.data_ptr() % 16 == 0:
+        if planes is not None and model._D % 4 == 0 and _float4_rows(ent, rel):
             key = (str(dev), st)
             nbytes = int(lib.kge_split_bf16x3_bytes(B, K))
             qp = _Q_PLANES.get(key)
@@ -132,19 +142,24 @@ def score_all(model, positive_sample: torch.Tensor, mode: str, out: torch.Tensor
             check(lib.kge_gemm_nt_bf16x3_planes(qp.data_ptr(), B, planes.data_ptr(), E, K, out.data_ptr(),
                                                 out.stride(0), B, E, st), "kge_gemm_nt_bf16x3_planes")
             return out
-        Q = torch.empty((B, K), dtype=torch.float32, device=dev)
-        check(lib.kge_eval_query(fq, m, ent.data_ptr(), E, ent.stride(0), rel.data_ptr(),
-                                 rel.shape[0], rel.stride(0), positive_sample.data_ptr(), B, model._D, Q.data_ptr(),
-                                 Q.stride(0), st), "kge_eval_query")
-        if planes is not None:
-            key = (str(dev), st)
-            qp = _Q_PLANES[key] = split_planes(Q, _Q_PLANES.get(key))
-            check(lib.kge_gemm_nt_bf16x3_planes(qp.data_ptr(), B, planes.data_ptr(), E, K, out.data_ptr(),
-                                                out.stride(0), B, E, st), "kge_gemm_nt_bf16x3_planes")
-        else:
-            check(lib.kge_gemm_nt_bf16x3(Q.data_ptr(), Q.stride(0), ent.data_ptr(), ent.stride(0), out.data_ptr(),
-                                         out.stride(0), B, E, K, st), "kge_gemm_nt_bf16x3")
-        return out
+        # the staging-split GEMM reads float4 quads of Q and of the table: K and the table's row stride multiples
+        # of 4, 16-B bases (Q is dense and freshly allocated). A table without planes that does not meet that
+        # (hidden_dim 50, a padded or offset view) takes the fused scorer below, which allocates nothing the size
+        # of the table (planes are usually missing because memory is short)
+        if planes is not None or (K % 4 == 0 and _float4_rows(ent)):
+            Q = torch.empty((B, K), dtype=torch.float32, device=dev)
+            check(lib.kge_eval_query(fq, m, ent.data_ptr(), E, ent.stride(0), rel.data_ptr(),
+                                     rel.shape[0], rel.stride(0), positive_sample.data_ptr(), B, model._D,
+                                     Q.data_ptr(), Q.stride(0), st), "kge_eval_query")
+            if planes is not None:
+                key = (str(dev), st)
+                qp = _Q_PLANES[key] = split_planes(Q, _Q_PLANES.get(key))
+                check(lib.kge_gemm_nt_bf16x3_planes(qp.data_ptr(), B, planes.data_ptr(), E, K, out.data_ptr(),
+                                                    out.stride(0), B, E, st), "kge_gemm_nt_bf16x3_planes")
+            else:
+                check(lib.kge_gemm_nt_bf16x3(Q.data_ptr(), Q.stride(0), ent.data_ptr(), ent.stride(0),
+                                             out.data_ptr(), out.stride(0), B, E, K, st), "kge_gemm_nt_bf16x3")
+            return out
     cand = torch.arange(E, device=dev, dtype=torch.int64).unsqueeze(0).expand(B, E)  # row stride 0
     modulus = float(model.modulus.detach().reshape(-1)[0]) if model.model_name == "pRotatE" else 0.0
     return ops.score_indexed_raw(FN_IDS[model.model_name], m, ent, rel, model._rel_off, positive_sample, cand,
@@ -155,11 +170,11 @@ _RANK_WS = {}
 
 
 def _planes_rank_ok(model, planes) -> bool:
-    """Whether the ranks-from-planes path applies: DistMult / ComplEx with entity planes, float4 rows."""
+    """Whether the ranks-from-planes path applies: DistMult / ComplEx with entity planes, float4 rows (D, both
+    tables' row strides and bases: kge_eval_query_planes' precondition)."""
     if model.model_name not in MFMA_FNS or planes is None:
         return False
-    ent, rel = model.entity_embedding, model.relation_embedding
-    return model._D % 4 == 0 and ent.data_ptr() % 16 == 0 and rel.data_ptr() % 16 == 0
+    return model._D % 4 == 0 and _float4_rows(model.entity_embedding, model.relation_embedding)
 
 
 def rank_planes(model, positive_sample: torch.Tensor, mode: str, planes: torch.Tensor, truth: torch.Tensor,
