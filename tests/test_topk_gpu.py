@@ -12,6 +12,7 @@ import torch
 import customknowledgegraphembedding_amd as kge
 from customknowledgegraphembedding_amd import evaluate
 from oracle import kge_oracle as O
+from tests import sweep_cases as W
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120)]
 DEV = "cuda"
@@ -38,28 +39,8 @@ def queries(g, E, R, B):
     return np.stack([g.randint(E, size=B), g.randint(R, size=B), g.randint(E, size=B)], 1)
 
 
-def reference(S, k, ptr=None, ids=None):
-    """The k best columns of each row of the CPU matrix S: (ids [M, k] int64, scores [M, k]), -1 / -inf padding."""
-    S = S.detach().cpu()
-    M, N = S.shape
-    out_i = torch.full((M, k), -1, dtype=torch.int64)
-    out_s = torch.full((M, k), float("-inf"), dtype=torch.float32)
-    for b in range(M):
-        valid = ~torch.isnan(S[b])
-        if ptr is not None:
-            x = torch.as_tensor(np.asarray(ids[int(ptr[b]):int(ptr[b + 1])], dtype=np.int64))
-            valid[x[(x >= 0) & (x < N)]] = False
-        cand = torch.nonzero(valid).reshape(-1)  # ascending id
-        s, order = torch.sort(S[b][cand], descending=True, stable=True)
-        n = min(k, len(cand))
-        out_i[b, :n] = cand[order[:n]]
-        out_s[b, :n] = s[:n]
-    return out_i, out_s
-
-
-def same(got, want):
-    gi, gs = got[0].cpu(), got[1].cpu()
-    return torch.equal(gi, want[0]) and torch.equal(gs.view(torch.int32), want[1].view(torch.int32))
+# the yardstick and the bitwise comparison, shared with test_sweep_widths_gpu.py
+reference, same = W.topk_reference, W.same_topk
 
 
 def random_exclude(g, E, B, most=12, extra=()):
