@@ -178,6 +178,11 @@ SIGNATURES = {
                                    ctypes.c_size_t, _c_p]),
     "kge_topk_rows": (_c_i, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64,
                              _c_p]),
+    "kge_eval_topk_planes_workspace_size": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    # (A_planes, a_rows, B_planes, b_rows, K, M, N, excl_ptr, excl_ids, nexcl, k, out_ids, ids_ld, out_scores,
+    #  scores_ld, workspace, workspace_bytes, stream)
+    "kge_eval_topk_planes": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64,
+                                    _c_p, _c_i64, _c_p, _c_i64, _c_p, ctypes.c_size_t, _c_p]),
     "kge_gemm_nt_bf16x3_planes_ex": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p,
                                             _c_p]),
     "kge_rank_filtered": (_c_i, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),

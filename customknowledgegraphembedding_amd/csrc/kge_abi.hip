@@ -1668,6 +1668,34 @@ int kge_topk_rows(const float* scores, int64_t M, int64_t N, int64_t ld, const i
     return check_launch("kge_topk_rows");
 }
 
+int64_t kge_eval_topk_planes_workspace_size(int64_t M, int64_t N, int64_t k) {
+    if (M < 0 || M > INT32_MAX || N <= 0 || N > INT32_MAX || k < 1 || k > kTopkMax) return 0;
+    return (M * eval_topk_planes_parts(N) * k * 8 + 15) / 16 * 16;
+}
+
+int kge_eval_topk_planes(const void* A_planes, int64_t a_rows, const void* B_planes, int64_t b_rows, int64_t K,
+                         int64_t M, int64_t N, const int64_t* excl_ptr, const int64_t* excl_ids, int64_t nexcl,
+                         int64_t k, int64_t* out_ids, int64_t ids_ld, float* out_scores, int64_t scores_ld,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (k < 1 || k > kTopkMax) return fail(KGE_EINVAL, "kge_eval_topk_planes: k must be 1 .. " + std::to_string(kTopkMax));
+    if (M < 0 || N <= 0 || K <= 0 || M > a_rows || N > b_rows || nexcl < 0) return fail(KGE_EINVAL, "bad shape");
+    if (M == 0) return ok();
+    if (!A_planes || !B_planes || !out_ids || !out_scores || !workspace || (nexcl > 0 && (!excl_ptr || !excl_ids)))
+        return fail(KGE_EINVAL, "null pointer");
+    if (M > INT32_MAX || N > INT32_MAX || ids_ld < k || scores_ld < k || !aligned(A_planes, 16) ||
+        !aligned(B_planes, 16) || !aligned(workspace, 16))
+        return fail(KGE_EINVAL, "kge_eval_topk_planes: int32 shapes, row strides >= k, 16-B aligned planes / workspace");
+    if (kge_split_bf16x3_bytes(a_rows, K) >= ((int64_t)1 << 32) - 16 ||
+        kge_split_bf16x3_bytes(b_rows, K) >= ((int64_t)1 << 32) - 16)
+        return fail(KGE_ENOTSUP, "kge_eval_topk_planes: planes past 4 GB");
+    if ((int64_t)workspace_bytes < kge_eval_topk_planes_workspace_size(M, N, k))
+        return fail(KGE_EINVAL, "kge_eval_topk_planes: workspace too small");
+    if (nexcl == 0) excl_ptr = excl_ids = nullptr;
+    launch_eval_topk_planes(A_planes, a_rows, B_planes, b_rows, K, (int)M, (int)N, excl_ptr, excl_ids, (int)k, out_ids,
+                            ids_ld, out_scores, scores_ld, workspace, (hipStream_t)stream);
+    return check_launch("kge_eval_topk_planes");
+}
+
 int kge_score_dense(int fn, int mode, const float* head, int64_t head_ld, const float* rel, int64_t rel_ld,
                     int64_t rel_off, const float* tail, int64_t tail_ld, int64_t B, int64_t N, int64_t D, float gamma,
                     float emb_range, float modulus, float* scores, int64_t scores_ld, void* stream) {

@@ -828,13 +828,24 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 512), amdgpu_waves_per_
 //     (a __syncthreads() fence would drain every copy in flight);
 //   * the loop is unrolled by 3 so that every stage access names its object.
 // Per accumulator the same products in the same order: C (and the counts) bitwise gemm_nt_x3p_kernel<.., 4>'s.
+// The epilogue is a template parameter (store, count, select the best k): the main loop is the same text for all.
 // ---------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* xl_lds_t;
+typedef __attribute__((address_space(3))) unsigned char* xl_ldsb_t;
+typedef __attribute__((address_space(3))) float* xl_ldsf_t;
 
-template <bool CNT>
+// the epilogues: store C; count the scores above the row's truth (kge_eval_rank_planes); keep the best k of the
+// tile's columns per row (kge_eval_topk_planes)
+constexpr int kEpiStore = 0, kEpiCount = 1, kEpiTopk = 2;
+constexpr int XL_PIECE = 32 * 128 * 4;  // kEpiTopk: one wave's 32 x 128 accumulators of half a tile
+static_assert(3 * XL_PIECE <= XS_STAGE, "three waves' pieces per stage buffer");
+
+template <int EPI>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, 512), amdgpu_waves_per_eu(2))) void gemm_nt_x3l_kernel(
     const __bf16* __restrict__ Ap, int64_t a_plane, const __bf16* __restrict__ Bp, int64_t b_plane, int kp,
-    float* __restrict__ C, int M, int N, int64_t ldc, const float* __restrict__ ts, int* __restrict__ gcnt) {
+    float* __restrict__ C, int M, int N, int64_t ldc, const float* __restrict__ ts, int* __restrict__ gcnt,
+    const int64_t* __restrict__ xptr, const int64_t* __restrict__ xids, int2* __restrict__ parts, int k) {
+    constexpr bool CNT = EPI == kEpiCount;
     __shared__ __attribute__((aligned(16))) unsigned char xl0[XS_STAGE];
     __shared__ __attribute__((aligned(16))) unsigned char xl1[XS_STAGE];
     __shared__ __attribute__((aligned(16))) unsigned char xl2[XS_STAGE];
@@ -945,6 +956,52 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 512), amdgpu_waves_per_
             }
         __syncthreads();
         if (t < XS_T && rowcnt[t] && m0 + t < M) atomicAdd(&gcnt[m0 + t], rowcnt[t]);
+        return;
+    }
+    if constexpr (EPI == kEpiTopk) {
+        // The tile's scores go through the stage buffers half a tile at a time (rows wr 64 + i 32 .. + 31 of every
+        // wave: 128 x 256 floats, each wave's 32 x 128 piece contiguous; pieces 0-2 in xl0, 3-5 in xl1, 6-7 in
+        // xl2), and each wave then selects 16 rows of its own row group as topk_rows_kernel does: lane per column,
+        // the columns ahead of the row's k-th entry (a ballot) offered in ascending column order. Every row < M
+        // stores its list, an empty one too: parts[row][tn][k].
+        auto piece = [&](int w) -> xl_ldsf_t {
+            const xl_ldsb_t b = w < 3 ? (xl_ldsb_t)xl0 : w < 6 ? (xl_ldsb_t)xl1 : (xl_ldsb_t)xl2;
+            return (xl_ldsf_t)(b + (w % 3) * XL_PIECE);
+        };
+        const xl_ldsf_t mine = piece(wave), left = piece(wave & ~1), right = piece(wave | 1);
+        __syncthreads();  // every wave is past its last fragment reads and every copy has landed: the stages are free
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            if (i) __syncthreads();  // the first half's rows are selected
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    mine[((r & 3) + 8 * (r >> 2) + 4 * half) * 128 + j * 32 + col] = acc[i][j][r];
+            __syncthreads();
+            for (int rr = 0; rr < 16; ++rr) {
+                const int lr = wc * 16 + rr;
+                const int gm = m0 + wr * 64 + i * 32 + lr;
+                if (gm >= M) break;  // wave-uniform
+                const int64_t xlo = xptr ? xptr[gm] : 0, xhi = xptr ? xptr[gm + 1] : 0;
+                float ms = -INFINITY;
+                int mi = kTopkEmpty;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int e = n0 + c * 64 + lane;
+                    const float v = (c < 2 ? left : right)[lr * 128 + (c & 1) * 64 + lane];
+                    const float ks = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ms), k - 1));
+                    const int ki = __builtin_amdgcn_readlane(mi, k - 1);
+                    uint64_t m = __ballot(e < N && topk_ahead(v, e, ks, ki));  // a NaN is ahead of nothing
+                    while (m) {
+                        const int j = __ffsll((unsigned long long)m) - 1;
+                        m &= m - 1;
+                        topk_offer(ms, mi, __shfl(v, j), n0 + c * 64 + j, k, lane, xids, xlo, xhi);
+                    }
+                }
+                if (lane < k) parts[((int64_t)gm * ntn + tn) * k + lane] = make_int2(__float_as_int(ms), mi);
+            }
+        }
         return;
     }
 #pragma unroll
@@ -1314,13 +1371,14 @@ void launch_x3p(const void* Ap, int64_t a_rows, const void* Bp, int64_t b_rows, 
                        N, ldc, ts, gcnt);
 }
 
-template <bool CNT>
+template <int EPI>
 void launch_x3l(const void* Ap, int64_t a_rows, const void* Bp, int64_t b_rows, int kp, float* C, int64_t ldc, int M,
-                int N, const float* ts, int* gcnt, hipStream_t st) {
+                int N, const float* ts, int* gcnt, hipStream_t st, const int64_t* xptr = nullptr,
+                const int64_t* xids = nullptr, int2* parts = nullptr, int k = 0) {
     const int64_t tiles = (int64_t)((M + XS_T - 1) / XS_T) * ((N + XS_T - 1) / XS_T);
-    hipLaunchKernelGGL((gemm_nt_x3l_kernel<CNT>), dim3((unsigned)tiles), dim3(512), 0, st,
+    hipLaunchKernelGGL((gemm_nt_x3l_kernel<EPI>), dim3((unsigned)tiles), dim3(512), 0, st,
                        static_cast<const __bf16*>(Ap), a_rows * kp, static_cast<const __bf16*>(Bp), b_rows * kp, kp, C, M,
-                       N, ldc, ts, gcnt);
+                       N, ldc, ts, gcnt, xptr, xids, parts, k);
 }
 
 int launch_gemm_nt_x3p(const void* Ap, int64_t a_rows, const void* Bp, int64_t b_rows, int64_t K, float* C, int64_t ldc,
@@ -1328,7 +1386,7 @@ int launch_gemm_nt_x3p(const void* Ap, int64_t a_rows, const void* Bp, int64_t b
     const int kp = (int)((K + 15) / 16 * 16);
     const int64_t tiles = (int64_t)((M + XS_T - 1) / XS_T) * ((N + XS_T - 1) / XS_T);
     if (form == 4) {  // LDS-DMA staging, three stages
-        launch_x3l<false>(Ap, a_rows, Bp, b_rows, kp, C, ldc, M, N, nullptr, nullptr, st);
+        launch_x3l<kEpiStore>(Ap, a_rows, Bp, b_rows, kp, C, ldc, M, N, nullptr, nullptr, st);
         return 0;
     }
     if (form == 3) {  // 256 x 192 block tiles
@@ -1364,7 +1422,7 @@ int launch_eval_rank_planes(const void* Ap, int64_t a_rows, const void* Bp, int6
                            F, ts, fs, gcnt);
     if (phases & 2) {
         if (form == 4)
-            launch_x3l<true>(Ap, a_rows, Bp, b_rows, kp, nullptr, 0, M, N, ts, gcnt, st);
+            launch_x3l<kEpiCount>(Ap, a_rows, Bp, b_rows, kp, nullptr, 0, M, N, ts, gcnt, st);
         else if (form == 3)
             launch_x3p<true, 3>(Ap, a_rows, Bp, b_rows, kp, nullptr, 0, M, N, ts, gcnt, st);
         else
@@ -1383,6 +1441,20 @@ int launch_rank_finish(int64_t M, int64_t N, const int64_t* truth, const int64_t
     const float* fs = reinterpret_cast<const float*>(static_cast<const unsigned char*>(ws) + ((M * 8 + 15) / 16 * 16));
     hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)((M + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0,
                        st, M, N, truth, fptr, fids, ts, fs, gcnt, ranks);
+    return 0;
+}
+
+int64_t eval_topk_planes_parts(int64_t N) { return (N + XS_T - 1) / XS_T; }
+
+int launch_eval_topk_planes(const void* Ap, int64_t a_rows, const void* Bp, int64_t b_rows, int64_t K, int M, int N,
+                            const int64_t* xptr, const int64_t* xids, int k, int64_t* out_ids, int64_t ids_ld,
+                            float* out_scores, int64_t scores_ld, void* ws, hipStream_t st) {
+    const int kp = (int)((K + 15) / 16 * 16);
+    launch_x3l<kEpiTopk>(Ap, a_rows, Bp, b_rows, kp, nullptr, 0, M, N, nullptr, nullptr, st, xptr, xids,
+                         static_cast<int2*>(ws), k);
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((M + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0,
+                       st, static_cast<const int2*>(ws), (int64_t)M, eval_topk_planes_parts(N), k, out_ids, ids_ld,
+                       out_scores, scores_ld);
     return 0;
 }
 

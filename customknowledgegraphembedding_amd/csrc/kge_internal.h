@@ -384,6 +384,12 @@ int launch_eval_rank_planes(const void* Ap, int64_t a_rows, const void* Bp, int6
 // rank_finish_kernel alone on a workspace of eval_rank_ws_bytes' layout (kge_eval_rank_sweep)
 int launch_rank_finish(int64_t M, int64_t N, const int64_t* truth, const int64_t* fptr, const int64_t* fids, void* ws,
                        int64_t* ranks, hipStream_t st);
+// kge_eval_topk_planes: the lists per query row (one per 256-column tile of the form-4 plane GEMM, whose selecting
+// epilogue stores them at ws[row][tile][k]) and the two launches (the GEMM, topk_merge_kernel)
+int64_t eval_topk_planes_parts(int64_t N);
+int launch_eval_topk_planes(const void* Ap, int64_t a_rows, const void* Bp, int64_t b_rows, int64_t K, int M, int N,
+                            const int64_t* xptr, const int64_t* xids, int k, int64_t* out_ids, int64_t ids_ld,
+                            float* out_scores, int64_t scores_ld, void* ws, hipStream_t st);
 // kge_eval_topk_sweep's merge of `parts` lists per row (topk_sweep_kernel's workspace), and kge_topk_rows
 int launch_topk_merge(const void* parts, int64_t B, int64_t nparts, int k, int64_t* out_ids, int64_t ids_ld,
                       float* out_scores, int64_t scores_ld, hipStream_t st);

@@ -18,7 +18,8 @@ path of TranSparse and of widths the sweep has no kernel for.
 
 predict answers a query instead of ranking a known truth: the k best entities for (h, r, ?) / (?, r, t) with their
 scores, known answers left out (exact filtered top-k: topk_sweep / kge_eval_topk_sweep for the distance functions,
-score_all + topk_rows / kge_topk_rows otherwise).
+score_all + topk_rows / kge_topk_rows otherwise; topk_planes / kge_eval_topk_planes for DistMult / ComplEx without the
+score matrix).
 """
 from __future__ import annotations
 
@@ -401,10 +402,62 @@ def topk_rows(scores: torch.Tensor, k: int, excl_ptr: torch.Tensor | None = None
     return out_ids, out_scores
 
 
+_TOPK_PLANES_WS = {}
+
+
+def topk_planes(model, positive_sample: torch.Tensor, mode: str, k: int, planes: torch.Tensor | None,
+                excl_ptr: torch.Tensor | None = None, excl_ids: torch.Tensor | None = None,
+                nexcl: int | None = None):
+    """(ids [B, k] int64, scores [B, k]) of the k best entities per query row for DistMult / ComplEx straight from
+    the entity planes, without the [B, E] score matrix (kge_eval_query_planes, then kge_eval_topk_planes: the plane
+    GEMM keeping the best k per 256-entity tile, then a merge), under topk_sweep's contract and with its argument
+    checks: topk_rows(score_all(..., planes=planes))'s ids and scores exactly. The workspace is k / 128 of the matrix
+    it replaces. None exactly where rank_planes answers None (another model, no planes, rows without float4 loads):
+    callers fall back to score_all + topk_rows."""
+    k = _check_k(k, "topk_planes")
+    if not _planes_rank_ok(model, planes):
+        return None
+    ent, rel = model.entity_embedding.detach(), model.relation_embedding.detach()
+    dev = ent.device
+    if positive_sample.dim() != 2 or positive_sample.shape[1] != 3:
+        raise ValueError("topk_planes: positive_sample must be [B, 3]")
+    B, E, K = positive_sample.shape[0], ent.shape[0], ent.shape[1]
+    if positive_sample.dtype != torch.int64 or not positive_sample.is_contiguous() or positive_sample.device != dev:
+        raise ValueError(f"topk_planes: positive_sample must be a contiguous int64 tensor on {dev}")
+    excl_ptr, excl_ids, nx = _check_excl("topk_planes", dev, B, excl_ptr, excl_ids, nexcl)
+    ops._need_gpu(ent, rel)
+    lib = _lib.load()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    key = (str(dev), st)
+    nbytes = int(lib.kge_split_bf16x3_bytes(B, K))
+    qp = _Q_PLANES.get(key)
+    if qp is None or qp.numel() < nbytes:
+        qp = _Q_PLANES[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    check(lib.kge_eval_query_planes(FN_IDS[model.model_name], ops.mode_id(mode), ent.data_ptr(), E, ent.stride(0),
+                                    rel.data_ptr(), rel.shape[0], rel.stride(0), positive_sample.data_ptr(), B,
+                                    model._D, qp.data_ptr(), B, st), "kge_eval_query_planes")
+    wsb = int(lib.kge_eval_topk_planes_workspace_size(B, E, k))
+    ws = _TOPK_PLANES_WS.get(key)
+    if ws is None or ws.numel() < wsb:
+        ws = _TOPK_PLANES_WS[key] = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, k), dtype=torch.int64, device=dev)
+    scores = torch.empty((B, k), dtype=torch.float32, device=dev)
+    check(lib.kge_eval_topk_planes(qp.data_ptr(), B, planes.data_ptr(), E, K, B, E,
+                                   None if excl_ptr is None else excl_ptr.data_ptr(),
+                                   None if excl_ids is None else excl_ids.data_ptr(), nx, k, ids.data_ptr(), k,
+                                   scores.data_ptr(), k, ws.data_ptr(), ws.numel(), st), "kge_eval_topk_planes")
+    return ids, scores
+
+
 # The functions predict sends through topk_sweep: those whose sweep measured faster than score_all + topk_rows by
 # DESIGN §3.0's rule (§3.4, profiles/r11_topk_ab.txt); the others, and every batch topk_sweep answers None for, take
 # the matrix path.
 TOPK_SWEEP_FNS = ("TransE", "RotatE", "pRotatE", "InterHT")
+# The functions predict sends through topk_planes, up to TOPK_PLANES_MAX_K, by the same rule (§3.4,
+# profiles/r15_topk_planes_ab.txt). Empty: the selecting epilogue has not measured faster than score_all +
+# topk_rows; topk_planes is there for callers short of the [B, E] matrix's memory.
+TOPK_PLANES_FNS = ()
+TOPK_PLANES_MAX_K = TOPK_MAX
 
 
 def predict(model, queries, mode: str, k: int = 10, known_triples=None, batch_size: int | None = None):
@@ -445,6 +498,8 @@ def predict(model, queries, mode: str, k: int = 10, known_triples=None, batch_si
                     xp = torch.from_numpy(p - p[0]).to(dev)
                     xi = torch.from_numpy(xids[p[0]:p[-1]]).to(dev)
             got = topk_sweep(model, pos, mode, k, xp, xi, nx) if sweep else None
+            if got is None and model.model_name in TOPK_PLANES_FNS and k <= TOPK_PLANES_MAX_K:
+                got = topk_planes(model, pos, mode, k, planes, xp, xi, nx)
             if got is None:
                 topk_rows(score_all(model, pos, mode, planes=planes), k, xp, xi, ids[s:s + bs], scores[s:s + bs])
             else:
@@ -655,4 +710,4 @@ def test_step(model, test_triples, all_true_triples, args=None, batch_size=None)
 
 
 __all__ = ["build_filter", "score_all", "rank_filtered", "rank_planes", "rank_sweep", "RankPipeline", "metrics_from_ranks", "test_step", "entity_planes",
-           "split_planes", "HEAD_BATCH", "TAIL_BATCH", "build_exclude", "topk_sweep", "topk_rows", "predict", "TOPK_MAX"]
+           "split_planes", "HEAD_BATCH", "TAIL_BATCH", "build_exclude", "topk_sweep", "topk_rows", "topk_planes", "predict", "TOPK_MAX"]
