@@ -96,6 +96,10 @@ SIGNATURES = {
     "kge_step_planner_set_board": (_c_i, [_c_p, _c_p, _c_i64]),
     "kge_step_planner_set_lead": (_c_i, [_c_p, _c_i]),
     "kge_step_planner_get": (_c_i, [_c_p, _c_i]),
+    "kge_step_planner_plan_size": (_c_i64, [_c_i, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),
+    "kge_step_planner_set_rows": (_c_i, [_c_p, _c_i]),
+    "kge_step_planned_rows": (_c_i, [_c_i, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i,
+                                     _c_i64, _c_p]),
     "kge_step_planner_set_clocks": (_c_i, [_c_p, _c_p, _c_i64]),
     "kge_step_planner_plan": (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_i]),
     "kge_step_planner_step": (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_i, _c_p, _c_p, _c_p, _c_p]),

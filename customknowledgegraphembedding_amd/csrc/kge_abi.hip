@@ -593,7 +593,7 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
             // next batch's plan
             const int64_t groups = (p.B + p.tile_rows - 1) / p.tile_rows;
             p.tile_blocks = (int)(groups * 8);
-            waves = (groups * 8 + (p.tile_next.plan ? plan_groups(p.tile_next.B, p.tile_next.R) : 0)) * kWavesPerBlock;
+            waves = (groups * 8 + (p.tile_next.plan ? p.tile_plan_blocks : 0)) * kWavesPerBlock;
             break;
         }
         case GRID_CAND_PER_WAVE:
@@ -761,7 +761,7 @@ int tile_plan(int fn, ScoreParams& p, const kge_forms* forms = nullptr) {
     // step_fwd_tile_kernel step 0), sized for the block's actual wave count
     const int64_t sort_ints = P2 ? (kTileSortMaxB + NT - 1) / NT * p.tile_waves * kTileSortRel : 0;
     auto lds = [&](int64_t R, int64_t QS) { return R * qrow + QS * opb + fixed + std::max(R * lrow, sort_ints * 4); };
-    int64_t R = kTileMaxRows;
+    int64_t R = kTileRows;
     if (forms && forms->tile_rows > 0) R = std::min<int64_t>(R, forms->tile_rows);
     while (R >= 1 && lds(R, 0) > kTileLdsMax) --R;
     if (R < 1) return 0;
@@ -794,6 +794,52 @@ int planned_tile_params(const Tables& t, int64_t B, int64_t N, ScoreParams& p, c
     a.ent = a.rel = reinterpret_cast<const float*>((uintptr_t)4096);
     fill_indexed(p, a, {KGE_TAIL_BATCH, nullptr, nullptr, 0, B, N});
     return tile_plan(t.fn, p, forms) ? p.tile_rows : 0;
+}
+
+// The LDS of a PLANNED instance at R rows per block (p.tile_waves set: tile_plan ran): the query images, the
+// relation slots and the small arrays. Its sorted list is the plan's, in global memory, so tile_plan's list region
+// (R (N + 1) ints, 16-65 KB) is not part of it, and InterHT's relation slots are counted again for the room that
+// leaves (C2 at 16 rows: 3 -> 7; at 17 rows: 5). 0 when R rows do not fit, or are more than the prologue's two
+// per wave. The tail blocks' plan_lds_ints are the launch's to add (step_forward_planned).
+int planned_tile_layout(int fn, ScoreParams& p, int64_t R) {
+    int V = 1, G = 1;
+    if (pick_vg(p, V, G)) return 0;
+    const int64_t opb = (int64_t)G * kWave * V * 4;
+    const int64_t qrow = tile_nq(fn) * opb + 8 + 8 + 8 + 4, fixed = kTileBuckets * 4 + 16;
+    auto lds = [&](int64_t r, int64_t qs) { return r * qrow + qs * opb + fixed; };
+    if (R < 1 || R > std::min(kTileMaxRows, 2 * p.tile_waves) || lds(R, 0) > kTileLdsMax) return 0;
+    int64_t QS = 0;
+    if (fn == KGE_INTERHT)
+        while (QS < R && lds(R, QS + 1) <= kTileLdsMax) ++QS;
+    p.tile_rows = (int)R;
+    p.tile_q2slots = (int)QS;
+    p.tile_lds = (int)lds(R, QS);
+    return 1;
+}
+
+// The planner's row rule (kge_step_planner_*): rows per group of a planned step whose launch also makes
+// the next plan. The launch's plan blocks follow its 8 ceil(B / R) scoring blocks in the grid, so they start at
+// once, beside the sweep, only where the scoring blocks leave CUs free. cap(R): the blocks of the step's instance
+// resident at once, at R rows' LDS (0: unknown). Where the library's R0 rows fill the device
+// (8 ceil(B / R0) > cap - 8) the answer is the smallest larger R that fits the planned LDS with at least the
+// relation slots tile_plan gives R0, whose plan fits plan_bytes (0: any), and that leaves 8 CUs; R0 when there is
+// none, or the capacity is unknown. waves: the step's waves per block.
+template <class Cap>
+int planned_rows_rule(const Tables& t, int64_t B, int64_t N, int waves, int64_t plan_bytes, Cap cap) {
+    ScoreParams tp;
+    const int R0 = planned_tile_params(t, B, N, tp);
+    if (!R0) return 0;
+    const int qs0 = tp.tile_q2slots;
+    if (waves) tp.tile_waves = waves;
+    const int64_t c0 = cap(R0);
+    if (c0 <= 0 || 8 * plan_groups(B, R0) <= c0 - 8) return R0;
+    for (int R = R0 + 1; R <= kTileMaxRows; ++R) {
+        if (!planned_tile_layout(t.fn, tp, R) || tp.tile_q2slots < qs0) continue;
+        if (plan_bytes > 0 && plan_words(B, N, R) * 4 > plan_bytes) continue;
+        const int64_t c = cap(R);
+        if (c > 0 && 8 * plan_groups(B, R) <= c - 8) return R;
+    }
+    return R0;
 }
 
 // The form of a planned step's sweep (kge_step_planner_set_form / _set_board / _set_lead): waves per block,
@@ -986,7 +1032,8 @@ int64_t kge_step_plan_size(int fn, int64_t nentity, int64_t ent_ld, int64_t nrel
     return step_plan_bytes({fn, nullptr, nentity, ent_ld, nullptr, nrelation, rel_ld, rel_off, D, 0.f, 0.f, 0.f}, B, N);
 }
 
-static int step_plan(const Tables& t, const Batch& b, void* plan, void* stream) {
+// rows: the rows per group (the planner's row rule or kge_step_planner_set_rows); 0: the library's
+static int step_plan(const Tables& t, const Batch& b, void* plan, void* stream, int rows = 0) {
     if (!valid_fn(t.fn)) return fail(KGE_EINVAL, "unknown score function id " + std::to_string(t.fn));
     if (b.mode != KGE_HEAD_BATCH && b.mode != KGE_TAIL_BATCH)
         return fail(KGE_EINVAL, "kge_step_plan needs a negative mode (0 or 1)");
@@ -996,6 +1043,7 @@ static int step_plan(const Tables& t, const Batch& b, void* plan, void* stream) 
     ScoreParams tp;
     if (!planned_tile_params(t, b.B, b.N, tp))
         return fail(KGE_ENOTSUP, "the tile form does not apply to this shape (kge_step_plan_size is 0)");
+    if (rows) tp.tile_rows = rows;
     const PlanArgs a = plan_args(tp, t, b, plan);
     const unsigned groups = (unsigned)plan_groups(b.B, tp.tile_rows);
     if (tp.tile_waves == 16)
@@ -1025,7 +1073,7 @@ struct StepOut {
 // batch `next` made into next_plan (null: none). sf: the planner's sweep form (null: the library's).
 static int step_forward_planned(const Tables& t, const Batch& b, float temperature, int adversarial, const void* plan,
                                 const Batch& next, void* next_plan, const StepOut& o, const SweepForm* sf,
-                                void* stream) {
+                                void* stream, int rows = 0, int* occ = nullptr, int plan_blocks = 0) {
     int rc = check_fn_mode(t.fn, b.mode);
     if (rc) return rc;
     if (b.mode == KGE_SINGLE) return fail(KGE_EINVAL, "kge_step_forward_planned needs a negative mode (0 or 1)");
@@ -1048,6 +1096,10 @@ static int step_forward_planned(const Tables& t, const Batch& b, float temperatu
     if (!R || !tile_plan(t.fn, p, &fm) || p.tile_rows != R)
         return fail(KGE_ENOTSUP, "the tile form does not apply to these tables (unaligned rows, or "
                                  "kge_step_plan_size is 0): use kge_step_forward");
+    // the planned instance's own LDS, at the plan's rows per group (rows; 0: the library's)
+    if (!planned_tile_layout(t.fn, p, rows ? rows : R))
+        return fail(KGE_ENOTSUP, "this many rows per group do not fit a block of the planned step");
+    tp.tile_rows = p.tile_rows;
     p.out = o.neg_scores;
     p.out_ld = o.ns_ld;
     p.pos_base = nullptr;
@@ -1071,10 +1123,14 @@ static int step_forward_planned(const Tables& t, const Batch& b, float temperatu
     // of its own 101.6 us, not planned 101.9 us; scripts/plan_probe.py, profiles/r05_plan_ab.txt)
     if (next_plan) {
         p.tile_next = plan_args(tp, t, next, next_plan);
+        // one plan block per group, or plan_blocks of them that share the groups (the planner's row rule)
+        const int ng = (int)plan_groups(next.B, tp.tile_rows);
+        p.tile_plan_blocks = (plan_blocks > 0 && p.tile_waves == kTileSharedWaves) ? std::min(plan_blocks, ng) : ng;
         p.tile_lds = std::max(p.tile_lds, plan_lds_ints(p.tile_waves * kWave) * 4);
     }
+    p.tile_occ = occ;
     rc = run_score(t.fn, b.mode, p, KIND_STEP_FWD_TILE, stream);
-    if (rc) return rc;
+    if (rc || occ) return rc;
     return launch_neg_rows(p, "kge_step_forward_planned row reductions", stream);
 }
 
@@ -1088,6 +1144,15 @@ int kge_step_forward_planned(int fn, int mode, const float* ent, int64_t nentity
     return step_forward_planned(t, {mode, nullptr, nullptr, 0, B, N}, temperature, adversarial, plan,
                                 {next_mode, next_pos, next_neg, next_neg_ld, B, N}, next_plan,
                                 {neg_scores, ns_ld, out_neg, pos_scores, out_pos}, nullptr, stream);
+}
+
+// Whether a planner applies the row rule unless kge_step_planner_set_rows says otherwise: as planned_sweep_defaults,
+// only what was measured and passed (profiles/r16_rows_ab.txt; each at ONE shape, B 512, N 256, d 1000).
+// C2 (InterHT) +2.0 %, C3 (RotatE) +4.6 %; C4 (DistMult d 500, N 1024: 2 KB rows, 17 x 1 025 items per plan group)
+// lost 18 % and keeps the library's rows and one plan block per group, as every other function and width does.
+int planner_row_rule(int fn, int64_t D) {
+    const int64_t row_bytes = D * 4 * (is_split(fn) ? 2 : 1);
+    return row_bytes >= 4096 && (fn == KGE_INTERHT || fn == KGE_ROTATE);
 }
 
 // The planned step loop as a handle (kge_step_planner_*): the tables, shapes and the two plan buffers are given
@@ -1111,12 +1176,22 @@ struct kge_step_planner {
     long long* clk = nullptr;  // kge_step_planner_set_clocks (profiling builds)
     int cus = 0;               // the device's CUs: the throttle needs every scoring block resident
     int64_t groups = 0;        // row groups of a batch (8 scoring blocks each)
+    // rows per group of the plans and steps to come: 0 until the first plan, which takes the library's, or the row
+    // rule's (planned_rows_rule) where planner_row_rule or kge_step_planner_set_rows says so (rule)
+    int rows = 0;
+    int rule = 0;
+    // plan blocks of a step's launch: 0 = one per group, at the launch's end; where the row rule found the scoring
+    // grid to leave 8 CUs free, 8 that share the groups and run beside the sweep
+    int plan_blocks = 0;
+    int64_t plan_bytes = 0;    // each plan buffer's size
     int64_t steps = 0;  // steps issued
     void* stream = nullptr;
 };
 
 // what the planner's next step runs (the setters' choices over the library's), and whether its throttle runs
-static SweepForm planner_form(const kge_step_planner* sp) {
+// (groups: the row groups the form is for; -1: the planner's current count)
+static SweepForm planner_form(const kge_step_planner* sp, int64_t groups = -1) {
+    if (groups < 0) groups = sp->groups;
     SweepForm f = {0, 0, 0, 0, sp->sweep ? (int)(sp->steps & 1) : 0, nullptr, sp->clk};
     planned_sweep_defaults(sp->t.fn, sp->t.D, f.waves, f.depth, f.lead);
     if (sp->waves) f.waves = sp->waves;
@@ -1124,8 +1199,71 @@ static SweepForm planner_form(const kge_step_planner* sp) {
     if (f.waves == 8) f.depth = 2;
     if (sp->lead >= 0) f.lead = sp->lead;
     f.tag = (int)(sp->steps % kSweepTagMask) + 1;  // 1 .. kSweepTagMask: a zeroed board holds no entry
-    if (sp->board && f.lead > 0 && sp->groups <= kSweepBoardLine && sp->groups * 8 <= sp->cus) f.board = sp->board;
+    if (sp->board && f.lead > 0 && groups <= kSweepBoardLine && groups * 8 <= sp->cus) f.board = sp->board;
     return f;
+}
+
+// The blocks of the planner's next step resident at once at R rows per group: the device's CUs times the blocks per
+// CU of the step's instance (the smaller of its head-batch and tail-batch instances) at that layout's LDS, from the
+// runtime's occupancy answer. 0: no device, or no answer. Nothing is launched.
+static int64_t planner_capacity(const kge_step_planner* sp, int R) {
+    if (sp->cus <= 0) return 0;
+    // (the throttle's instance is the form's where every block is resident)
+    const SweepForm sf = planner_form(sp, plan_groups(sp->B, R));
+    int per_cu = INT32_MAX;
+    float* const none = reinterpret_cast<float*>(sp->plans[0]);  // stands for every buffer: nothing runs
+    const int64_t* const ids = reinterpret_cast<const int64_t*>(sp->plans[0]);
+    for (int mode : {KGE_HEAD_BATCH, KGE_TAIL_BATCH}) {
+        int occ = 0;
+        if (step_forward_planned(sp->t, {mode, nullptr, nullptr, 0, sp->B, sp->N}, sp->temperature, sp->adversarial,
+                                 sp->plans[0], {mode, ids, ids, sp->N, sp->B, sp->N}, sp->plans[1],
+                                 {none, sp->N, none, none, none}, &sf, sp->stream, R, &occ, 8))
+            return 0;
+        per_cu = std::min(per_cu, occ);
+    }
+    return (int64_t)sp->cus * per_cu;
+}
+
+// the rows per group of the planner's plans and steps, chosen at the first plan (capacity unknown: the library's)
+static int planner_rows(kge_step_planner* sp) {
+    if (!sp->rows) {
+        sp->rows = planned_rows_rule(sp->t, sp->B, sp->N, planner_form(sp).waves, sp->plan_bytes,
+                                     [&](int R) { return sp->rule ? planner_capacity(sp, R) : 0; });
+        if (plan_groups(sp->B, sp->rows) > sp->groups) sp->clk = nullptr;  // (a clock record is sized for its groups)
+        sp->groups = plan_groups(sp->B, sp->rows);
+        const int64_t cap = sp->rule ? planner_capacity(sp, sp->rows) : 0;
+        sp->plan_blocks = (cap > 0 && 8 * sp->groups <= cap - 8) ? 8 : 0;
+    }
+    return sp->rows;
+}
+
+int64_t kge_step_planner_plan_size(int fn, int64_t nentity, int64_t ent_ld, int64_t nrelation, int64_t rel_ld,
+                                   int64_t rel_off, int64_t B, int64_t N, int64_t D) {
+    const Tables t = {fn, nullptr, nentity, ent_ld, nullptr, nrelation, rel_ld, rel_off, D, 0.f, 0.f, 0.f};
+    if (!valid_fn(fn)) return 0;
+    ScoreParams tp;
+    const int R0 = planned_tile_params(t, B, N, tp);
+    int64_t words = 0;
+    for (int R = R0; R0 && R <= kTileMaxRows; ++R) words = std::max(words, plan_words(B, N, R));
+    return words * 4;
+}
+
+int kge_step_planned_rows(int fn, int64_t nentity, int64_t ent_ld, int64_t nrelation, int64_t rel_ld, int64_t rel_off,
+                          int64_t B, int64_t N, int64_t D, int waves, int64_t capacity, int* out) {
+    if (!valid_fn(fn)) return fail(KGE_EINVAL, "unknown score function id " + std::to_string(fn));
+    if (!out || (waves != 0 && waves != 8 && waves != 12 && waves != 16))
+        return fail(KGE_EINVAL, "kge_step_planned_rows: out[4]; waves 0, 8, 12 or 16");
+    const Tables t = {fn, nullptr, nentity, ent_ld, nullptr, nrelation, rel_ld, rel_off, D, 0.f, 0.f, 0.f};
+    const int R = planned_rows_rule(t, B, N, waves, 0, [&](int) { return capacity; });
+    ScoreParams tp;
+    if (!R || !planned_tile_params(t, B, N, tp)) return fail(KGE_ENOTSUP, "the tile form does not apply to this shape");
+    if (waves) tp.tile_waves = waves;
+    if (!planned_tile_layout(fn, tp, R)) return fail(KGE_ENOTSUP, "the rows do not fit this wave count");
+    out[0] = R;
+    out[1] = tp.tile_q2slots;
+    out[2] = std::max(tp.tile_lds, plan_lds_ints(tp.tile_waves * kWave) * 4);
+    out[3] = (int)(8 * plan_groups(B, R));
+    return ok();
 }
 
 int kge_step_planner_create(kge_step_planner** out, int fn, const float* ent, int64_t nentity, int64_t ent_ld,
@@ -1149,6 +1287,8 @@ int kge_step_planner_create(kge_step_planner** out, int fn, const float* ent, in
     sp->plans[0] = plan0;
     sp->plans[1] = plan1;
     sp->stream = stream;
+    sp->plan_bytes = plan_bytes;
+    sp->rule = planner_row_rule(fn, D);
     ScoreParams tp;
     sp->groups = plan_groups(B, planned_tile_params(t, B, N, tp));
     int dev = 0;
@@ -1169,8 +1309,30 @@ int kge_step_planner_set_form(kge_step_planner* sp, int waves, int depth) {
         if (planned_tile_params(sp->t, sp->B, sp->N, tw, &fm) != planned_tile_params(sp->t, sp->B, sp->N, tp))
             return fail(KGE_ENOTSUP, "kge_step_planner_set_form: this wave count changes the rows per group");
     }
+    if (waves && sp->rows > 2 * waves)  // (the planned prologue builds at most two rows per wave)
+        return fail(KGE_ENOTSUP, "kge_step_planner_set_form: this wave count changes the rows per group");
     sp->waves = waves;
     sp->depth = depth;
+    return ok();
+}
+
+int kge_step_planner_set_rows(kge_step_planner* sp, int rows) {
+    if (!sp) return fail(KGE_EINVAL, "kge_step_planner_set_rows: null pointer");
+    const bool chosen = rows > 0 || rows < KGE_PLANNER_ROWS_RULE;  // (a refused call changes nothing)
+    if (chosen) {
+        ScoreParams tp;
+        if (rows < 0 || !planned_tile_params(sp->t, sp->B, sp->N, tp)) return fail(KGE_EINVAL, "kge_step_planner_set_rows: bad rows");
+        tp.tile_waves = planner_form(sp).waves;
+        if (!planned_tile_layout(sp->t.fn, tp, rows))
+            return fail(KGE_ENOTSUP, "kge_step_planner_set_rows: this many rows do not fit a block of this form");
+        if (plan_words(sp->B, sp->N, rows) * 4 > sp->plan_bytes)
+            return fail(KGE_EINVAL, "kge_step_planner_set_rows: the plan buffers are too small (kge_step_planner_plan_size)");
+        if (plan_groups(sp->B, rows) > sp->groups) sp->clk = nullptr;  // (a clock record is sized for its groups)
+        sp->groups = plan_groups(sp->B, rows);
+    }
+    sp->rule = rows == KGE_PLANNER_ROWS_RULE || (rows == 0 && planner_row_rule(sp->t.fn, sp->t.D));
+    sp->plan_blocks = 0;
+    sp->rows = chosen ? rows : 0;
     return ok();
 }
 
@@ -1200,6 +1362,9 @@ int kge_step_planner_get(const kge_step_planner* sp, int what) {
         case KGE_PLANNER_LEAD: return f.lead;
         case KGE_PLANNER_THROTTLE: return f.board != nullptr;
         case KGE_PLANNER_TAG: return f.tag;
+        case KGE_PLANNER_ROWS: return sp->rows;
+        case KGE_PLANNER_PLAN_BLOCKS:
+            return !sp->rows ? 0 : (sp->plan_blocks > 0 && f.waves == kTileSharedWaves) ? (int)std::min<int64_t>(sp->plan_blocks, sp->groups) : (int)sp->groups;
         default: return -1;
     }
 }
@@ -1235,7 +1400,7 @@ int kge_step_planner_set_sweep(kge_step_planner* sp, int alternate) {
 int kge_step_planner_plan(kge_step_planner* sp, const int64_t* pos, const int64_t* neg, int64_t neg_ld, int mode) {
     if (!sp) return fail(KGE_EINVAL, "kge_step_planner_plan: null pointer");
     const int buf = sp->cur < 0 ? 0 : sp->cur;
-    const int rc = step_plan(sp->t, {mode, pos, neg, neg_ld, sp->B, sp->N}, sp->plans[buf], sp->stream);
+    const int rc = step_plan(sp->t, {mode, pos, neg, neg_ld, sp->B, sp->N}, sp->plans[buf], sp->stream, planner_rows(sp));
     if (rc) return rc;
     sp->cur = buf;
     sp->mode = mode;
@@ -1247,12 +1412,14 @@ int kge_step_planner_step(kge_step_planner* sp, const int64_t* next_pos, const i
     if (!sp) return fail(KGE_EINVAL, "kge_step_planner_step: null pointer");
     if (sp->cur < 0) return fail(KGE_EINVAL, "kge_step_planner_step: no batch planned (kge_step_planner_plan first)");
     const bool nxt = next_pos && next_neg;
+    const int rows = planner_rows(sp);
     const SweepForm sf = planner_form(sp);
     const int rc = step_forward_planned(sp->t, {sp->mode, nullptr, nullptr, 0, sp->B, sp->N}, sp->temperature,
                                         sp->adversarial, sp->plans[sp->cur],
                                         {next_mode, next_pos, next_neg, next_neg_ld, sp->B, sp->N},
                                         nxt ? sp->plans[1 - sp->cur] : nullptr,
-                                        {neg_scores, sp->N, out_neg, pos_scores, out_pos}, &sf, sp->stream);
+                                        {neg_scores, sp->N, out_neg, pos_scores, out_pos}, &sf, sp->stream, rows,
+                                        nullptr, sp->plan_blocks);
     if (rc) return rc;
     ++sp->steps;
     if (nxt) {

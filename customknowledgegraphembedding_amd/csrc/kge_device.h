@@ -1176,8 +1176,9 @@ __global__ __launch_bounds__(NWV * kWave) void tile_plan_kernel(PlanArgs a) {
 
 // PLANNED: the instances of a planned step (p.tile_plan; launch_tile chooses): rows, ids and sorted items come from
 // the plan, and steps 0-2 below are replaced by the planned prologue. BOARD (planned only): the lead throttle; an
-// instance without it holds none of the board's instructions.
-template <int FN, bool CH, int V, int G, int NWV, int DEPTH, bool PLANNED = false, bool BOARD = false>
+// instance without it holds none of the board's instructions. SHARED (planned, 12 waves only): fewer plan blocks
+// than the next plan has groups, each taking several (the loop costs ~40 VGPRs, so the other instances hold none).
+template <int FN, bool CH, int V, int G, int NWV, int DEPTH, bool PLANNED = false, bool BOARD = false, bool SHARED = false>
 __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams p) {
     static_assert(DEPTH == 1 || DEPTH == 2, "candidate rows in flight per wave");
     static_assert(PLANNED || !BOARD, "the board belongs to a planned step");
@@ -1201,8 +1202,20 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     if constexpr (PLANNED) {
         if (p.tile_next.plan && (int)blockIdx.x >= p.tile_blocks) {
-            // a tail block: the NEXT batch's plan, on the CUs the scoring blocks free up at the end of the launch
-            tile_plan_group<NWV>(p.tile_next, (int)blockIdx.x - p.tile_blocks, reinterpret_cast<int*>(tile_smem));
+            // a tail block: the NEXT batch's plan
+            // (one block per group, on the CUs the scoring blocks free up at the end of the launch; or, where the
+            // scoring grid leaves CUs free, one block per free CU, beside the sweep: the dispatcher starts no further
+            // block of the grid on a CU a plan block has left before scoring blocks exit, so a plan block takes
+            // every tile_plan_blocks-th group itself. DESIGN 3.0)
+            if constexpr (SHARED) {
+                const int ng = (int)plan_groups(p.tile_next.B, p.tile_next.R);
+                for (int g = (int)blockIdx.x - p.tile_blocks; g < ng; g += p.tile_plan_blocks) {
+                    tile_plan_group<NWV>(p.tile_next, g, reinterpret_cast<int*>(tile_smem));
+                    __syncthreads();  // the next group reuses the LDS
+                }
+            } else {
+                tile_plan_group<NWV>(p.tile_next, (int)blockIdx.x - p.tile_blocks, reinterpret_cast<int*>(tile_smem));
+            }
 #ifdef KGE_PROFILING_KNOBS
             if (p.tile_clk && t == 0) {  // (kge_internal.h: the clock record) the plan block's entry and thread 0's exit
                 long long* const pc = p.tile_clk + (int64_t)p.tile_blocks * kSweepClkMarks + 2 * ((int)blockIdx.x - p.tile_blocks);
@@ -1241,7 +1254,10 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
         // round trip 1: the header, the slice's bounds, the rows this wave builds (A: row w; B: row w + NWV where
         // the block has fewer waves than rows) and, lane r, row r of the group (the relation runs; wave 0 also puts
         // the rows' ids into LDS for the sweep). The plan holds R rows per group, -1 past the batch.
-        constexpr bool TWO = NWV < kTileMaxRows;
+        // (C: where the block has at least kTileRows waves, the few rows past them under the planner's row rule,
+        // row w + NWV built by wave w after its own: one more round trip for those waves, no more registers)
+        constexpr bool TWO = NWV < kTileRows;
+        static_assert(TWO || kTileMaxRows <= 2 * NWV, "two rows per wave (8 and 12 waves: the host caps the rows)");
         const int* so = pl + plan_soff(p.B, R) + (int64_t)gi * 9;
         const bool hasA = w < nr, hasB = TWO && w + NWV < nr;
         const int rA = hasA ? w : 0, rB = hasB ? w + NWV : rA;
@@ -1288,13 +1304,14 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
         // the relation ids in its lanes; the run's first row's wave fills the slot
         [[maybe_unused]] vecf<V> t2a[G], t2b[G];
         [[maybe_unused]] int slA = -1, slB = -1;
+        [[maybe_unused]] int slv = -1;  // lane r: row r's relation slot
         if constexpr (FN == KGE_INTERHT) {
             static_assert(kTileMaxRows <= kWave, "one lane per row");
             const int prev = __shfl_up(relv, 1, kWave);
             const bool open = inl && (lane == 0 || relv != prev);
             const uint64_t m = __ballot(open);
             const int sl = __popcll(m & (lane == 63 ? ~0ull : (2ull << lane) - 1)) - 1;
-            const int slv = (inl && sl < QS) ? sl : -1;
+            slv = (inl && sl < QS) ? sl : -1;
             if (w == 0 && inl) q2slot[lane] = slv;
             auto third = [&](int r, bool has, int& slot, vecf<V>* t2) {
                 const int s = __builtin_amdgcn_readlane(slv, r);
@@ -1340,6 +1357,23 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
                 if (slB >= 0) {
 #pragma unroll
                     for (int k = 0; k < G; ++k) q2img[(size_t)slB * W + lane + k * kWave] = t2b[k];
+                }
+            }
+        }
+        if constexpr (!TWO) {
+            if (w + NWV < nr) {  // wave-uniform
+                const int rC = w + NWV;
+                Query<FN, CH, V, G> qc;
+                build_m(pmeta[rC], true, qc);
+                put_q(rC, qc);
+                if constexpr (FN == KGE_INTERHT) {
+                    const int s = __builtin_amdgcn_readlane(slv, rC), sp = __builtin_amdgcn_readlane(slv, rC - 1);
+                    const int ri = __builtin_amdgcn_readlane(relv, rC);
+                    if (s >= 0 && sp != s) {  // the run's first row fills its slot
+                        const rsrc_t sr = make_rsrc(p.rel + (ri >= 0 ? ri : 0) * p.r_ld + p.r_off, ri >= 0 ? (uint32_t)p.D * 4u : 0u);
+#pragma unroll
+                        for (int k = 0; k < G; ++k) q2img[(size_t)s * W + lane + k * kWave] = bload<V>(sr, goff<V>(lane, k));
+                    }
                 }
             }
         }
@@ -1483,7 +1517,7 @@ __global__ __launch_bounds__(NWV * kWave) void step_fwd_tile_kernel(ScoreParams 
             }
             if (lane == 0) rrow[r] = rok ? ri : -1;
         };
-        if constexpr (2 * NWV <= kTileMaxRows) {
+        if constexpr (2 * NWV <= kTileRows) {
             for (int r = w; r < nr; r += 2 * NWV) {
                 const int r2 = r + NWV < nr ? r + NWV : r;
                 Query<FN, CH, V, G> qa, qb;
@@ -4115,14 +4149,22 @@ namespace kge_impl {
 // ---------------------------------------------------------------------------------------------
 // dispatch over (kind, candidate side, vector width, groups per lane) for one score function
 // ---------------------------------------------------------------------------------------------
-template <int FN, bool CH, int V, int G, int NWV, int DEPTH, bool PLANNED, bool BOARD>
+template <int FN, bool CH, int V, int G, int NWV, int DEPTH, bool PLANNED, bool BOARD, bool SHARED = false>
 void launch_tile_as(const ScoreParams& p, hipStream_t st, int blocks) {
     // up to the whole 160 KB of a CU's LDS per block (set once per instantiation)
     static const bool lds_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH, PLANNED, BOARD>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH, PLANNED, BOARD, SHARED>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kTileLdsMax) == hipSuccess;
     (void)lds_ok;
-    hipLaunchKernelGGL((step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH, PLANNED, BOARD>), dim3(blocks),
+    if (p.tile_occ) {  // the planner's row rule asks what is resident at once; nothing is launched
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH, PLANNED, BOARD, SHARED>,
+                                                         NWV * kWave, (size_t)p.tile_lds) != hipSuccess)
+            n = 0;
+        *p.tile_occ = n;
+        return;
+    }
+    hipLaunchKernelGGL((step_fwd_tile_kernel<FN, CH, V, G, NWV, DEPTH, PLANNED, BOARD, SHARED>), dim3(blocks),
                        dim3(NWV * kWave), p.tile_lds, st, p);
 }
 
@@ -4133,8 +4175,14 @@ void launch_tile(const ScoreParams& p, hipStream_t st, int blocks) {
     if (!p.tile_plan) {
         if constexpr (DEPTH == 2) launch_tile_as<FN, CH, V, G, NWV, 2, false, false>(p, st, blocks);
     } else if (p.tile_board && (p.tile_blocks >> 3) <= kSweepBoardLine) {
+        if constexpr (NWV == kTileSharedWaves) {
+            if (tile_plan_shared(p)) return launch_tile_as<FN, CH, V, G, NWV, DEPTH, true, true, true>(p, st, blocks);
+        }
         launch_tile_as<FN, CH, V, G, NWV, DEPTH, true, true>(p, st, blocks);
     } else {
+        if constexpr (NWV == kTileSharedWaves) {
+            if (tile_plan_shared(p)) return launch_tile_as<FN, CH, V, G, NWV, DEPTH, true, false, true>(p, st, blocks);
+        }
         launch_tile_as<FN, CH, V, G, NWV, DEPTH, true, false>(p, st, blocks);
     }
 }

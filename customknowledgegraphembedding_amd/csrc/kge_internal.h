@@ -133,7 +133,10 @@ constexpr bool kind_has(int k, int fn, bool ch, int G) {
            (kKinds[k].ch || !ch);
 }
 constexpr int kTileBuckets = 256;  // entity buckets of a slice (the block's counting sort)
-constexpr int kTileMaxRows = 16;
+constexpr int kTileRows = 16;     // rows per block the library takes when they fit (tile_plan)
+// the most rows a block of a planned step holds (the planner's row rule, kge_step_planner_set_rows): it sizes the
+// row arrays, the one-lane-per-row ballots and the planned prologue's two rows per wave (so also <= 2 x the waves)
+constexpr int kTileMaxRows = 20;
 constexpr int kTileLdsMax = 160 * 1024;
 constexpr int kTileSortRel = 64;     // relation buckets of the tile kernel's row sort (ids >= 62 share one)
 constexpr int kTileSortMaxB = 2048;  // batch rows the tile kernel sorts by relation in LDS
@@ -247,8 +250,12 @@ struct ScoreParams {
     int tile_dry;         // step_fwd_tile_kernel: setup only, no scoring (A/B knob KGE_TILE_DRY)
     int tile_rev;         // step_fwd_tile_kernel: sweep each block's sorted list in descending entity order
     const int* tile_plan; // step_fwd_tile_kernel: this batch's plan (kge_step_forward_planned), or null
+    int* tile_occ;        // host only: launch_tile_as launches nothing and answers here how many blocks of the
+                          // instance, at tile_lds bytes of LDS, one CU holds (0: the runtime could not tell)
     int tile_blocks;      // step_fwd_tile_kernel: scoring blocks; blocks past them make the next batch's plan
     PlanArgs tile_next;   // ... that plan (tile_next.plan null: none)
+    int tile_plan_blocks; // ... how many: one per group of the plan, or (kTileSharedWaves waves) fewer, plan block j
+                          // making the plan's groups j, j + tile_plan_blocks, ...
     // kge_eval_rank_sweep (rank_pairs_kernel, rank_sweep_kernel; tile_rows / tile_lds: the sweep's rows per block
     // and dynamic LDS bytes)
     struct {
@@ -346,6 +353,11 @@ struct ScoreParams {
     float reg3;       // 3 lambda: every element x of row e gets reg3 x |x| added to its gradient before Adam
     float* reg_part;  // sum |x|^3 of what each wave holds: [E] (bwd_ent_kernel), [E, 4] (bwd_ent_stream_kernel)
 };
+// the wave count whose planned instances exist with the plan-sharing loop (SHARED: the row rule's shapes run 12 waves)
+constexpr int kTileSharedWaves = 12;
+inline bool tile_plan_shared(const ScoreParams& p) {
+    return p.tile_next.plan && p.tile_plan_blocks < plan_groups(p.tile_next.B, p.tile_next.R);
+}
 
 // Adam coefficients of step t (1-based), computed on the host in double
 struct AdamArgs {

@@ -199,7 +199,9 @@ class StepPlanner:
         self.fn, self.ent, self.rel, self.rel_off, self.D = fn, ent, rel, rel_off, D
         self.B, self.N = B, N
         lib = _lib.load()
-        nbytes = self.plan_size(fn, ent, rel, rel_off, D, B, N)
+        # (a plan buffer for any rows per group: set_rows)
+        nbytes = int(lib.kge_step_planner_plan_size(fn, ent.shape[0], ent.stride(0), rel.shape[0], rel.stride(0),
+                                                    rel_off, B, N, D))
         if nbytes <= 0:
             raise _lib.KGEHipError("kge_step_plan_size is 0: the tile form does not apply to this shape "
                                    "(use step_forward_raw)")
@@ -253,15 +255,22 @@ class StepPlanner:
         choice for the row width (kge_step_planner_set_form)."""
         check(self._lib.kge_step_planner_set_form(self._h, int(waves), int(depth)), "kge_step_planner_set_form")
 
+    def set_rows(self, rows):
+        """Batch rows per group of the plans and steps to come (up to 20 where they fit); 0: the library's (16);
+        -1: the library's row rule chooses at the next plan (kge_step_planner_set_rows). form()["rows"] tells."""
+        check(self._lib.kge_step_planner_set_rows(self._h, int(rows)), "kge_step_planner_set_rows")
+
     def set_lead(self, lead):
         """The lead throttle: buckets (1..255) a wave may lead the slowest block of its slice before it naps once;
         0: off; -1: the library's choice for the row width (kge_step_planner_set_lead)."""
         check(self._lib.kge_step_planner_set_lead(self._h, int(lead)), "kge_step_planner_set_lead")
 
     def form(self):
-        """What the next step runs: {"waves", "depth", "lead", "throttle", "tag"} (kge_step_planner_get)."""
+        """What the next step runs: {"waves", "depth", "lead", "throttle", "tag", "rows", "plan_blocks"}
+        (kge_step_planner_get; rows and plan_blocks: 0 before the first plan)."""
         return {k: int(self._lib.kge_step_planner_get(self._h, i))
-                for i, k in enumerate(("waves", "depth", "lead", "throttle", "tag"))}
+                for k, i in (("waves", 0), ("depth", 1), ("lead", 2), ("throttle", 3), ("tag", 4), ("rows", 6),
+                             ("plan_blocks", 7))}
 
     def set_modulus(self, modulus):
         check(self._lib.kge_step_planner_set_modulus(self._h, float(modulus)), "kge_step_planner_set_modulus")

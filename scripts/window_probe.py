@@ -5,7 +5,8 @@
 and 24 and the board's own cost. Device us per step, events around 300 steps after 50 warmup, rounds
 interleaved, same batches as bench.py; outputs compared bitwise.
 (4) `timeline` (the same profiling library): where a planned step's launch spends its time outside the sweep.
-Usage: python scripts/window_probe.py skew [wl..] | timeline [wl..] | forms [wl..] | tune [wl..]"""
+`timeline=ROWS`: the same at ROWS rows per group (StepPlanner.set_rows; -1: the library's row rule).
+Usage: python scripts/window_probe.py skew [wl..] | timeline[=ROWS] [wl..] | forms [wl..] | tune [wl..]"""
 import json
 import os
 import statistics
@@ -29,11 +30,13 @@ CLK_MARKS = CLK_WAVE + 2 * 16
 
 
 def set_clocks(p, B):
-    """Hands the planner a zeroed clock record; returns (row groups, the record)."""
-    groups = (B + 15) // 16  # 16 rows per group; the library refuses a buffer smaller than its own count
+    """Hands the planner a zeroed clock record; returns (row groups, the record). After the planner's first plan:
+    it chooses its rows per group there."""
+    rows = p.form()["rows"]
+    assert rows > 0, "set_clocks before the planner's first plan: its rows per group are not chosen yet"
+    groups = (B + rows - 1) // rows  # the library refuses a buffer smaller than its own count
     clk = torch.zeros(groups * (8 * CLK_MARKS + 2), dtype=torch.int64, device=dev)
-    assert p._lib.kge_step_planner_set_clocks(p._h, clk.data_ptr(), clk.numel() * 8 - 8) != 0, \
-        "the tile plan has fewer than 16 rows per group for this shape: size the clock buffer from its groups"
+    assert p._lib.kge_step_planner_set_clocks(p._h, clk.data_ptr(), clk.numel() * 8 - 8) != 0
     check(p._lib.kge_step_planner_set_clocks(p._h, clk.data_ptr(), clk.numel() * 8), "kge_step_planner_set_clocks")
     return groups, clk
 
@@ -67,9 +70,9 @@ def skew(wl):
     for waves, depth, lead in ((12, 2, 0), (12, 1, 0), (16, 1, 0), (12, 2, 16), (16, 2, 0)):
         r = runner(m, batches, fn, waves, depth, lead)
         p = r.planner
-        groups, clk = set_clocks(p, w["B"])
         for i in range(40):
             r(i)
+        groups, clk = set_clocks(p, w["B"])
         spreads, durs, one_xcc = [], [], True
         for i in range(40, 46):
             clk.zero_()
@@ -96,17 +99,19 @@ def skew(wl):
             "slice_blocks_share_one_xcc": one_xcc}), flush=True)
 
 
-def timeline(wl):
+def timeline(wl, rows=None):
     """The planned step's launch as a timeline, in the library's own sweep form: per mark, the median and the worst
     (latest) block, in us after the step's earliest block entry, over six sampled steps of both modes; the plan
     (tail) blocks' earliest and latest entry and exit; the latest exit of any block."""
     w = bench.WORKLOADS[wl]
     m, batches = bench.make_inputs(w, 0, dev)
     r = bench.StepRunner(m, batches, FN_IDS[w["fn"]], planned=True)
-    groups, clk = set_clocks(r.planner, w["B"])
-    nsc = 8 * groups
+    if rows is not None:
+        r.planner.set_rows(rows)
     for i in range(40):
         r(i)
+    groups, clk = set_clocks(r.planner, w["B"])
+    nsc = 8 * groups
     marks = {k: [] for k in ("sweep_start", "wave0_sweep_end", "last_wave_sweep_end", "block_exit")}
     plan_in, plan_out, last = [], [], []
     for i in range(40, 46):
@@ -139,7 +144,8 @@ def timeline(wl):
     if plan_in:
         pi, po = torch.cat(plan_in), torch.cat(plan_out)
         out["plan_blocks"] = {"entry_earliest": round(float(pi.min()), 2), "entry_latest": round(float(pi.max()), 2),
-                              "exit_earliest": round(float(po.min()), 2), "exit_latest": round(float(po.max()), 2)}
+                              "exit_earliest": round(float(po.min()), 2), "exit_latest": round(float(po.max()), 2),
+                              "entries_of_last_sampled_step": [round(float(v), 1) for v in plan_in[-1].sort().values]}
     out["latest_exit_of_any_block"] = {"median_over_steps": round(statistics.median(last), 2), "max": round(max(last), 2)}
     print(json.dumps(out), flush=True)
     del m, batches
@@ -187,10 +193,11 @@ def forms(wl, tune=False):
 
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "forms"
+    what, _, rows = what.partition("=")
     for wl in (sys.argv[2:] or (["c2", "c3", "c4"] if what in ("forms", "timeline") else ["c2"])):
         if what == "skew":
             skew(wl)
         elif what == "timeline":
-            timeline(wl)
+            timeline(wl, int(rows) if rows else None)
         else:
             forms(wl, tune=what == "tune")
