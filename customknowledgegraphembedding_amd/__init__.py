@@ -9,7 +9,8 @@ from ._lib import FN_IDS, HEAD_BATCH, SINGLE, TAIL_BATCH, KGEHipError, build_id,
 from .model import KGEModel, TFKGEModel  # noqa: F401
 from . import ops  # noqa: F401
 from . import evaluate  # noqa: F401  (test_step, predict)
+from .evaluate import FilterTable  # noqa: F401  (the evaluation filter's true-answer table on the GPU)
 from .sampler import DeviceTrainDataset  # noqa: F401  (training batches drawn on the GPU)
 
-__all__ = ["TFKGEModel", "KGEModel", "ops", "evaluate", "DeviceTrainDataset", "load", "build_id", "KGEHipError",
+__all__ = ["TFKGEModel", "KGEModel", "ops", "evaluate", "DeviceTrainDataset", "FilterTable", "load", "build_id", "KGEHipError",
            "FN_IDS", "HEAD_BATCH", "TAIL_BATCH", "SINGLE"]

@@ -245,6 +245,14 @@ SIGNATURES = {
     # (blob, blob_bytes, idx, B, N, row0, mode, seed, step, step_ptr, pos, neg, neg_ld, weight, stream)
     "kge_dsampler_sample": (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i, ctypes.c_uint64, _c_i64, _c_p,
                                    _c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "kge_filter_table_size": (_c_i64, [_c_i64]),
+    "kge_filter_table_build": (_c_i, [_c_p, _c_i64, _c_p, _c_i64]),
+    "kge_eval_filter_workspace_size": (_c_i64, [_c_i64]),
+    # (blob, blob_bytes, mode, pos, M, drop_own, ptr, workspace, workspace_bytes, stream)
+    "kge_eval_filter_count": (_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_i64, _c_i, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    # (blob, blob_bytes, mode, pos, M, drop_own, ptr, ids, ids_capacity, workspace, workspace_bytes, stream)
+    "kge_eval_filter_fill": (_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_i64, _c_i, _c_p, _c_p, _c_i64, _c_p,
+                                    ctypes.c_size_t, _c_p]),
     "kge_transparse_score": (_c_i, [_c_i, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64,
                                     _c_i64, _c_i64, _c_i64, _c_f, _c_p, _c_i64, _c_p, _c_p]),
     "kge_transparse_score_workspace_size": (ctypes.c_size_t, [_c_i, _c_i64, _c_i64, _c_i64]),

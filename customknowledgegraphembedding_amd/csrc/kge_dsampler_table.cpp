@@ -7,12 +7,12 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <algorithm>
 #include <string>
 #include <vector>
 
 #include "kge_dsampler.h"
 #include "kge_hip.h"
+#include "kge_truth_csr.h"
 
 namespace kge_impl {
 int set_error(int code, const char* msg);  // kge_abi.hip
@@ -22,40 +22,20 @@ namespace {
 
 using namespace kge_impl;
 
-struct Key {
-    int64_t a, b, c;  // group key (a, b), candidate c
-    int64_t i;        // the triple
-    bool operator<(const Key& o) const {
-        if (a != o.a) return a < o.a;
-        if (b != o.b) return b < o.b;
-        return c < o.c;
-    }
-};
+using Key = TruthKey;
 
 // One mode's CSR from the triples sorted by (group key, candidate): rows in key order, each row's distinct
-// candidates ascending. Fills row[i] per triple, group[i] = triples (duplicates included) sharing i's key,
-// ptr / ids; returns the rows, or -1 when a list covers every entity.
+// candidates ascending (truth_csr). Fills row[i] per triple, group[i] = triples (duplicates included) sharing i's
+// key, ptr / ids; returns the rows, or -1 when a list covers every entity.
 int64_t build_mode(std::vector<Key>& keys, int64_t E, int64_t* row, int64_t* group, int64_t* ptr, int64_t* ids) {
-    std::sort(keys.begin(), keys.end());
-    const size_t T = keys.size();
-    int64_t rows = 0, n = 0;
-    ptr[0] = 0;
-    for (size_t s = 0; s < T;) {
-        size_t e = s;
-        const int64_t start = n;
-        while (e < T && keys[e].a == keys[s].a && keys[e].b == keys[s].b) {
-            if (n == start || ids[n - 1] != keys[e].c) ids[n++] = keys[e].c;
-            ++e;
-        }
-        if (n - start >= E) return -1;
+    return truth_csr(keys, ptr, ids, [&](int64_t r, size_t s, size_t e, int64_t len) {
+        if (len >= E) return false;
         for (size_t k = s; k < e; ++k) {
-            row[keys[k].i] = rows;
+            row[keys[k].i] = r;
             group[keys[k].i] = (int64_t)(e - s);
         }
-        ptr[++rows] = n;
-        s = e;
-    }
-    return rows;
+        return true;
+    });
 }
 
 }  // namespace
@@ -92,9 +72,7 @@ int kge_dsampler_table_build(const int64_t* triples, int64_t ntriples, int64_t n
     std::vector<int64_t> group[2];
     for (int mode = 0; mode < 2; ++mode) {
         for (int64_t i = 0; i < T; ++i) {
-            const int64_t h = triples[3 * i], r = triples[3 * i + 1], t = triples[3 * i + 2];
-            // head-batch: true_head[(r, t)] holds heads; tail-batch: true_tail[(h, r)] holds tails
-            keys[(size_t)i] = mode == KGE_HEAD_BATCH ? Key{r, t, h, i} : Key{h, r, t, i};
+            keys[(size_t)i] = truth_key(triples, i, mode == KGE_HEAD_BATCH);
         }
         group[mode].resize((size_t)T);
         // ptr needs at most T + 1 words and ids at most T: the ids start where ptr's bound ends and are

@@ -20,6 +20,12 @@ predict answers a query instead of ranking a known truth: the k best entities fo
 scores, known answers left out (exact filtered top-k: topk_sweep / kge_eval_topk_sweep for the distance functions,
 score_all + topk_rows / kge_topk_rows otherwise; topk_planes / kge_eval_topk_planes for DistMult / ComplEx without the
 score matrix).
+
+The filter lists themselves (the other true answers of each query) are made on the GPU: FilterTable holds the true
+triples as a keyed table (kge_filter_table_build, two sorts on the host, uploaded once) and FilterTable.csr looks
+any queries up in it (kge_eval_filter_count / kge_eval_filter_fill: build_filter's and build_exclude's CSR exactly);
+test_step and predict make the CSR of a whole pass with one call per mode and hand the batches views of it.
+build_filter / build_exclude remain as the host path (filter_on="host") and the yardstick.
 """
 from __future__ import annotations
 
@@ -304,6 +310,105 @@ def build_exclude(queries: np.ndarray, mode: str, triples) -> tuple[np.ndarray, 
     return ptr, ids
 
 
+_MODE_IDS = {"head-batch": HEAD_BATCH, "tail-batch": TAIL_BATCH}
+FILTER_SCAN_TILE = 4096  # kFtScanTile (csrc/kge_filter.h): the queries kge_eval_filter_count's scan takes per pass
+
+
+class FilterTable:
+    """The true answers of a set of triples as a table on the device (kge_filter_table_build: per mode the
+    distinct (r, t) / (h, r) keys in ascending order with their sorted distinct heads / tails, found by two sorts;
+    layout in csrc/kge_filter.h), from which `csr` makes build_filter's and build_exclude's CSR for any queries on
+    the GPU. Built once and uploaded; pass it to test_step / predict in place of the triples to reuse it over
+    validation passes. Ids are any int64 >= 0 (a negative id: KGEHipError)."""
+
+    def __init__(self, triples, device=None):
+        triples = np.ascontiguousarray(np.asarray(triples, dtype=np.int64).reshape(-1, 3))
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.KGEHipError(f"FilterTable needs a GPU device, got {self.device} (build_filter / "
+                                   "build_exclude make the CSR on the host)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.ntriples = len(triples)
+        self.table = torch.from_numpy(build_filter_table(triples)).to(self.device)
+
+    def csr(self, queries, mode: str, drop_own: bool = True):
+        """(ptr [M + 1], ids [ptr[M]]) on the device and ptr on the host (a numpy copy: the call's one host sync) for
+        the query triples [M, 3] (a contiguous int64 tensor on the table's device, or anything np.asarray takes):
+        build_filter(queries, mode, triples) with drop_own, build_exclude(queries, mode, triples) without, exactly.
+        Runs on the current stream (kge_eval_filter_count, kge_eval_filter_fill)."""
+        if mode not in _MODE_IDS:
+            raise ValueError("FilterTable.csr: mode must be 'head-batch' or 'tail-batch'")
+        dev = self.device
+        if torch.is_tensor(queries):
+            if queries.dim() != 2 or queries.shape[1] != 3:
+                raise ValueError("FilterTable.csr: queries must be [M, 3]")
+            if queries.dtype != torch.int64 or not queries.is_contiguous() or queries.device != dev:
+                raise ValueError(f"FilterTable.csr: queries must be a contiguous int64 tensor on {dev}")
+            pos = queries
+        else:
+            q = np.asarray(queries)
+            if q.size and (q.ndim != 2 or q.shape[1] != 3):
+                raise ValueError("FilterTable.csr: queries must be [M, 3]")
+            pos = torch.from_numpy(np.array(q, dtype=np.int64).reshape(-1, 3)).to(dev)  # a copy: q may be read-only
+        lib = _lib.load()
+        M, m, own = pos.shape[0], _MODE_IDS[mode], 1 if drop_own else 0
+        st = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            ws = torch.empty(int(lib.kge_eval_filter_workspace_size(M)), dtype=torch.uint8, device=dev)
+            ptr = torch.empty(M + 1, dtype=torch.int64, device=dev)
+            blob, nbytes = self.table.data_ptr(), self.table.numel() * 8
+            check(lib.kge_eval_filter_count(blob, nbytes, m, pos.data_ptr(), M, own, ptr.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), st), "kge_eval_filter_count")
+            ptr_host = ptr.cpu().numpy()
+            total = int(ptr_host[M])
+            ids = torch.empty(total, dtype=torch.int64, device=dev)
+            check(lib.kge_eval_filter_fill(blob, nbytes, m, pos.data_ptr(), M, own, ptr.data_ptr(),
+                                           ids.data_ptr() if total else None, total, ws.data_ptr(), ws.numel(), st),
+                  "kge_eval_filter_fill")
+        return ptr, ids, ptr_host
+
+
+def build_filter_table(triples) -> np.ndarray:
+    """The filter table of `triples` [T, 3] as a host int64 array (kge_filter_table_build: layout in
+    csrc/kge_filter.h), cut to the words in use."""
+    triples = np.ascontiguousarray(np.asarray(triples, dtype=np.int64).reshape(-1, 3))
+    lib = _lib.load()
+    nbytes = int(lib.kge_filter_table_size(len(triples)))
+    blob = np.empty(nbytes // 8, dtype=np.int64)
+    check(lib.kge_filter_table_build(triples.ctypes.data, len(triples), blob.ctypes.data, nbytes),
+          "kge_filter_table_build")
+    return blob[:int(blob[1])].copy()
+
+
+def _device_table(triples, dev, filter_on):
+    """The FilterTable test_step / predict look their filters up in, or None for the host path (filter_on="host",
+    tables off the GPU, or triples the table build refuses: a negative id)."""
+    if filter_on not in ("device", "host"):
+        raise ValueError("filter_on must be 'device' or 'host'")
+    if isinstance(triples, FilterTable):
+        if filter_on == "host":
+            raise ValueError("filter_on='host' needs the triples, not a FilterTable")
+        if triples.device != dev:
+            raise ValueError(f"the FilterTable is on {triples.device}, the model on {dev}")
+        return triples
+    if filter_on == "host" or dev.type != "cuda":
+        return None
+    try:
+        return FilterTable(triples, dev)
+    except _lib.KGEHipError:
+        return None
+
+
+def _batch_ptrs(ptr_dev: torch.Tensor, M: int, bs: int) -> torch.Tensor:
+    """[batches, bs + 1]: row i holds ptr[i bs .. i bs + bs] - ptr[i bs] (the batch's CSR starts rebased to 0; past
+    M the last start repeats), one gather for the whole pass."""
+    dev = ptr_dev.device
+    start = torch.arange(0, max(M, 1), bs, device=dev, dtype=torch.int64).unsqueeze(1)
+    idx = (start + torch.arange(bs + 1, device=dev, dtype=torch.int64).unsqueeze(0)).clamp_(max=M)
+    return (ptr_dev[idx] - ptr_dev[start]).contiguous()
+
+
 def _check_k(k, what):
     if int(k) != k or not 1 <= int(k) <= TOPK_MAX:
         raise ValueError(f"{what}: k must be in 1 .. {TOPK_MAX}, got {k}")
@@ -460,13 +565,16 @@ TOPK_PLANES_FNS = ()
 TOPK_PLANES_MAX_K = TOPK_MAX
 
 
-def predict(model, queries, mode: str, k: int = 10, known_triples=None, batch_size: int | None = None):
+def predict(model, queries, mode: str, k: int = 10, known_triples=None, batch_size: int | None = None,
+            filter_on: str = "device"):
     """Link prediction: for each query triple the k best entities in the candidate slot, (h, r, ?) for tail-batch
     and (?, r, t) for head-batch (the slot's own value is ignored), as (ids [M, k] int64, scores [M, k]) on the
-    model's device: score descending, ties by ascending id, padded with -1 / -inf. With `known_triples`, the
-    answers they already hold for a query are left out (build_exclude). Batches of `batch_size` (1 024) queries run
-    through topk_sweep where it applies and through score_all + topk_rows otherwise (DistMult / ComplEx from the
-    entity planes made once per call). There is no CPU fallback."""
+    model's device: score descending, ties by ascending id, padded with -1 / -inf. With `known_triples` (an array
+    of triples, or a FilterTable of them to reuse over calls), the answers they already hold for a query are left
+    out: the exclusion lists of all queries come from one FilterTable.csr call on the GPU and the batches slice
+    them; filter_on="host" (and triples the table refuses: a negative id) makes them with build_exclude instead.
+    Batches of `batch_size` (1 024) queries run through topk_sweep where it applies and through score_all +
+    topk_rows otherwise (DistMult / ComplEx from the entity planes made once per call). There is no CPU fallback."""
     k = _check_k(k, "predict")
     if mode not in ("head-batch", "tail-batch"):
         raise ValueError("predict: mode must be 'head-batch' or 'tail-batch'")
@@ -481,22 +589,31 @@ def predict(model, queries, mode: str, k: int = 10, known_triples=None, batch_si
         raise ValueError("predict: batch_size must be positive")
     ids = torch.empty((M, k), dtype=torch.int64, device=dev)
     scores = torch.empty((M, k), dtype=torch.float32, device=dev)
-    ptr = xids = None
+    ptr = xids = table = q_dev = None
     if known_triples is not None:
-        ptr, xids = build_exclude(q, mode, known_triples)
+        table = _device_table(known_triples, dev, filter_on)
+        if table is None:
+            ptr, xids = build_exclude(q, mode, known_triples)
+        else:
+            q_dev = torch.from_numpy(q).to(dev)
+            ptr_dev, xids, ptr = table.csr(q_dev, mode, drop_own=False)
+            bptr = _batch_ptrs(ptr_dev, M, bs)
     with torch.no_grad():
         planes = entity_planes(model)  # once per call (DistMult / ComplEx)
         sweep = model.model_name in TOPK_SWEEP_FNS
         for s in range(0, M, bs):
-            pos = torch.from_numpy(q[s:s + bs]).to(dev)
+            pos = torch.from_numpy(q[s:s + bs]).to(dev) if q_dev is None else q_dev[s:s + bs]
             xp = xi = None
             nx = 0
             if ptr is not None:
                 p = ptr[s:s + len(pos) + 1]
                 nx = int(p[-1] - p[0])
-                if nx:
+                if nx and table is None:
                     xp = torch.from_numpy(p - p[0]).to(dev)
                     xi = torch.from_numpy(xids[p[0]:p[-1]]).to(dev)
+                elif nx:  # views of the pass's CSR (8-B aligned: every reader loads the ids one by one)
+                    xp = bptr[s // bs, :len(pos) + 1]
+                    xi = xids[int(p[0]):int(p[-1])]
             got = topk_sweep(model, pos, mode, k, xp, xi, nx) if sweep else None
             if got is None and model.model_name in TOPK_PLANES_FNS and k <= TOPK_PLANES_MAX_K:
                 got = topk_planes(model, pos, mode, k, planes, xp, xi, nx)
@@ -648,10 +765,14 @@ def countries_auc_pr(model, test_triples, regions):
     return {"auc_pr": average_precision(np.array(y_true), y_score)}
 
 
-def test_step(model, test_triples, all_true_triples, args=None, batch_size=None):
+def test_step(model, test_triples, all_true_triples, args=None, batch_size=None, filter_on="device"):
     """Upstream `KGEModel.test_step(model, test_triples, all_true_triples, args)`: filtered MRR,
     MR and HITS@{1,3,10} over head-batch and tail-batch ranking of every test triple; with
-    args.countries, the AUC-PR over args.regions instead."""
+    args.countries, the AUC-PR over args.regions instead. The filter lists come from a FilterTable of
+    `all_true_triples` (which may be one already, to reuse it over validation passes): the test triples go to the
+    device once, one FilterTable.csr call per mode makes the whole pass's CSR on the GPU and the batches take views
+    of it. filter_on="host" (and triples the table refuses: a negative id) builds them with build_filter on the
+    host instead: the same ranks."""
     if args is not None and getattr(args, "countries", False):
         return countries_auc_pr(model, test_triples, args.regions)
     bs = batch_size or int(getattr(args, "test_batch_size", 1024) or 1024)
@@ -664,16 +785,53 @@ def test_step(model, test_triples, all_true_triples, args=None, batch_size=None)
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
     if world > 1:
         triples = triples[dist.get_rank()::world]
+    table = _device_table(all_true_triples, dev, filter_on)
+    modes = ("head-batch", "tail-batch")
     all_ranks = []
     with torch.no_grad():
         planes = entity_planes(model)  # once per evaluation pass (DistMult / ComplEx)
-        if _planes_rank_ok(model, planes) and len(triples):
+        sweep = _sweep_rank_ok(model)
+        if table is not None and len(triples):
+            # everything the batches read is made here, on the caller's stream, before the pipeline (whose streams
+            # wait for the caller's in its constructor) exists: the pass's CSRs, the rebased batch starts and the
+            # truth columns. The batches' ids are views of csr's tensors, which live until the ranks are on the host
+            M = len(triples)
+            pos_all = torch.from_numpy(np.array(triples)).to(dev)  # a copy: the caller's array may be read-only
+            csr = {m: table.csr(pos_all, m, drop_own=True) for m in modes}
+            bptr = {m: _batch_ptrs(csr[m][0], M, bs) for m in modes}
+            truth = {m: pos_all[:, 0 if m == "head-batch" else 2].contiguous() for m in modes}
+            starts = range(0, M, bs)
+            pipe = None
+            if _planes_rank_ok(model, planes):
+                # ranks straight from the planes (no [B, E] score matrix), batches pipelined over two streams
+                maxf = max(int(ph[min(s + bs, M)] - ph[s]) for _, _, ph in csr.values() for s in starts)
+                pipe = RankPipeline(model, planes, min(bs, M), maxf)
+            for mode in modes:
+                _, ids_dev, ph = csr[mode]
+                for s in starts:
+                    n = min(bs, M - s)
+                    pos, tr = pos_all[s:s + n], truth[mode][s:s + n]
+                    fptr = bptr[mode][s // bs, :n + 1]
+                    # an 8-B aligned view: every reader of the filter ids loads them one by one
+                    fids = ids_dev[int(ph[s]):int(ph[s + n])]
+                    nf = int(ph[s + n] - ph[s])
+                    if pipe is not None:
+                        all_ranks.append(pipe.submit(pos, mode, tr, fptr, fids, nf))
+                        continue
+                    r = rank_sweep(model, pos, mode, tr, fptr, fids, nf) if sweep else None
+                    if r is None:
+                        r = rank_filtered(score_all(model, pos, mode, planes=planes), tr, fptr, fids)
+                    all_ranks.append(r)
+            if pipe is not None:
+                pipe.flush()
+            all_ranks = [r.cpu().numpy() for r in all_ranks]
+        elif _planes_rank_ok(model, planes) and len(triples):
             # ranks straight from the planes (no [B, E] score matrix), batches pipelined over two streams
-            filt = {m: build_filter(triples, m, all_true_triples) for m in ("head-batch", "tail-batch")}
+            filt = {m: build_filter(triples, m, all_true_triples) for m in modes}
             starts = range(0, len(triples), bs)
             maxf = max(int(ptr[min(s + bs, len(triples))] - ptr[s]) for ptr, _ in filt.values() for s in starts)
             pipe = RankPipeline(model, planes, min(bs, len(triples)), maxf)
-            for mode in ("head-batch", "tail-batch"):
+            for mode in modes:
                 col = 0 if mode == "head-batch" else 2
                 ptr, ids = filt[mode]
                 for s in starts:
@@ -684,8 +842,7 @@ def test_step(model, test_triples, all_true_triples, args=None, batch_size=None)
                                                  torch.from_numpy(ids[p[0]:p[-1]]), int(p[-1] - p[0])))
             pipe.flush()
             all_ranks = [r.cpu().numpy() for r in all_ranks]
-        sweep = _sweep_rank_ok(model)
-        for mode in (() if all_ranks else ("head-batch", "tail-batch")):
+        for mode in (() if all_ranks else modes):
             col = 0 if mode == "head-batch" else 2
             ptr, ids = build_filter(triples, mode, all_true_triples)
             for s in range(0, len(triples), bs):
@@ -710,4 +867,5 @@ def test_step(model, test_triples, all_true_triples, args=None, batch_size=None)
 
 
 __all__ = ["build_filter", "score_all", "rank_filtered", "rank_planes", "rank_sweep", "RankPipeline", "metrics_from_ranks", "test_step", "entity_planes",
-           "split_planes", "HEAD_BATCH", "TAIL_BATCH", "build_exclude", "topk_sweep", "topk_rows", "topk_planes", "predict", "TOPK_MAX"]
+           "split_planes", "HEAD_BATCH", "TAIL_BATCH", "build_exclude", "topk_sweep", "topk_rows", "topk_planes", "predict", "TOPK_MAX",
+           "FilterTable", "build_filter_table"]

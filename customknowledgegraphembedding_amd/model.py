@@ -135,12 +135,14 @@ class _KGEBase(nn.Module):
                                  positive_sample, negative_sample, self._D, self._gamma_f,
                                  self._range_f, rel_off=self._rel_off, modulus=modulus)
 
-    def predict(self, queries, mode, k=10, known_triples=None, batch_size=None):
+    def predict(self, queries, mode, k=10, known_triples=None, batch_size=None, filter_on="device"):
         """The k best entities (ids [M, k] int64, scores [M, k]) for each query (h, r, ?) (tail-batch) or (?, r, t)
-        (head-batch), without the answers `known_triples` already hold: evaluate.predict."""
+        (head-batch), without the answers `known_triples` (triples, or an evaluate.FilterTable of them) already
+        hold: evaluate.predict."""
         from . import evaluate
 
-        return evaluate.predict(self, queries, mode, k=k, known_triples=known_triples, batch_size=batch_size)
+        return evaluate.predict(self, queries, mode, k=k, known_triples=known_triples, batch_size=batch_size,
+                                filter_on=filter_on)
 
     def extra_repr(self):
         return (f"model_name={self.model_name}, nentity={self.nentity}, nrelation={self.nrelation}, "
