@@ -327,12 +327,17 @@ struct RelAdam {
 };
 
 constexpr int kRelWaves = 16;  // waves per relation chunk: each scans 1/16 of the slots (fewer dependent rounds)
+// LAZY (kge_train_step_lazy; needs ra.on): a block whose relation none of the 2B slots uses leaves its columns and
+// their moments as they are. Every wave scans its slots whether or not its chunk holds used columns, and the waves'
+// ballots are OR-ed block-wide. A template parameter: the dense instance is the code it was.
+template <bool LAZY>
 __global__ __launch_bounds__(kRelWaves * kWave) void bwd_rel_kernel(const int64_t* __restrict__ pos, int64_t B, int64_t R,
                                                          const float* __restrict__ qg_rel, int64_t rel_w,
                                                          int64_t rel_off, float* __restrict__ d_rel, int64_t rel_ld,
                                                          int64_t rel_dim, const float* __restrict__ dmod_part,
                                                          float* __restrict__ d_mod, RelAdam ra) {
     __shared__ float red[kRelWaves][kWave];
+    __shared__ int hit_s[LAZY ? kRelWaves : 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (blockIdx.x == 0 && threadIdx.x == 0 && d_mod && dmod_part) {
         float m = 0.f;
@@ -348,10 +353,13 @@ __global__ __launch_bounds__(kRelWaves * kWave) void bwd_rel_kernel(const int64_
     const int64_t S = 2 * B, per = (S + kRelWaves - 1) / kRelWaves;
     const int64_t s_lo = w * per, s_hi = min(S, s_lo + per);
     float acc = 0.f;
-    if (__ballot(used)) {
+    bool hit = false;
+    (void)hit;
+    if (LAZY || __ballot(used)) {
         for (int64_t s0 = s_lo; s0 < s_hi; s0 += kWave) {
             const int64_t s = s0 + lane;
             unsigned long long m = __ballot(s < s_hi && pos[(s % B) * 3 + 1] == rho);  // slot s: row s % B
+            if constexpr (LAZY) hit = hit || m != 0ull;
             while (m) {
                 float v[8];
                 int nv = 0;
@@ -372,7 +380,16 @@ __global__ __launch_bounds__(kRelWaves * kWave) void bwd_rel_kernel(const int64_
         }
     }
     red[w][lane] = acc;
+    if constexpr (LAZY) {
+        if (lane == 0) hit_s[w] = hit ? 1 : 0;
+    }
     __syncthreads();
+    if constexpr (LAZY) {
+        int any = 0;
+#pragma unroll
+        for (int ww = 0; ww < kRelWaves; ++ww) any |= hit_s[ww];
+        if (!any) return;  // untouched relation: nothing of it is read or written
+    }
     if (w != 0 || c >= rel_dim) return;
     float g = 0.f;
 #pragma unroll
@@ -580,8 +597,9 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
             waves = p.B;  // one wave per slot / batch row
             break;
         case GRID_BLOCK_PER_ROW: waves = p.B * kWavesPerBlock; break;
-        case GRID_WAVE_PER_ENT: waves = p.c_rows; break;
-        case GRID_BLOCK_PER_ENT: waves = p.c_rows * kWavesPerBlock; break;
+        // (the lazy step's phase 2: one wave / block per entry of the touched rows' list)
+        case GRID_WAVE_PER_ENT: waves = p.lz_list ? p.lz_rows : p.c_rows; break;
+        case GRID_BLOCK_PER_ENT: waves = (p.lz_list ? p.lz_rows : p.c_rows) * kWavesPerBlock; break;
         case GRID_XCD_SLICES:
             waves = (p.B + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock * 8;
             if (kind == KIND_STEP_FWD_XCD && p.xcd_phases > 1) waves *= p.xcd_phases;
@@ -2078,6 +2096,10 @@ struct StepOpts {
     float *reg_part = nullptr, *reg_chunk = nullptr;  // workspace: per-wave partials [4 E], chunk sums
     const float* loss_parts = nullptr;                // [2] positive and negative sample loss
     float *loss = nullptr, *loss_sum = nullptr, *log = nullptr;
+    // kge_train_step_lazy (needs the fused Adam on both tables): phase 2 visits only the rows with events, listed
+    // in the workspace behind the scan, and the relation update leaves relations no slot uses
+    bool lazy = false;
+    int *lz_list = nullptr, *lz_count = nullptr, *lz_tiles = nullptr;
 };
 
 static EvArgs ev_args(const Batch& b, int64_t E) {
@@ -2244,6 +2266,20 @@ static int step_backward_impl(const Tables& t, const Batch& b, const StepGrads& 
     const float reg3 = adam ? 3.f * o.reg : 0.f;
     q.reg3 = reg3;
     q.reg_part = o.reg_part;
+    if (o.lazy && t.nentity > 0) {
+        // the touched rows, ascending, from the global bucket offsets (two launches; kge_scan.h)
+        const int ntot = (int)(B * N + 3 * B);
+        const int64_t lt = (t.nentity + kTile4k - 1) / kTile4k;
+        q.lz_rows = std::min<int64_t>(t.nentity, ntot);
+        q.lz_list = o.lz_list;
+        q.lz_count = o.lz_count;
+        hipLaunchKernelGGL(lazy_count_kernel, dim3((unsigned)lt), dim3(kScanTile), 0, st, w.off, t.nentity, ntot,
+                           o.lz_tiles);
+        hipLaunchKernelGGL(lazy_list_kernel, dim3((unsigned)lt), dim3(kScanTile), 0, st, w.off, t.nentity, ntot,
+                           o.lz_tiles, o.lz_list, (int)q.lz_rows, o.lz_count);
+        rc = check_launch("kge_train_step_lazy row list");
+        if (rc) return rc;
+    }
     if (t.nentity > 0) {
         // streaming form (block per row, waves split the columns) under the same condition as phase 1
         rc = run_score(fn, mode, q, stream_form(G1) ? KIND_BWD_ENT_STREAM : KIND_BWD_ENT, stream);
@@ -2277,8 +2313,14 @@ static int step_backward_impl(const Tables& t, const Batch& b, const StepGrads& 
             ra.on = 1;
             ra.reg3 = reg3;
         }
-        hipLaunchKernelGGL(bwd_rel_kernel, dim3((unsigned)rb), dim3(kRelWaves * kWave), 0, st, b.pos, B, t.nrelation,
-                           w.qg_rel, rel_w, t.rel_off, g.d_rel, t.rel_ld, rel_dim, w.dmod, g.d_modulus, ra);
+        if (o.lazy && ra.on)
+            hipLaunchKernelGGL(bwd_rel_kernel<true>, dim3((unsigned)rb), dim3(kRelWaves * kWave), 0, st, b.pos, B,
+                               t.nrelation, w.qg_rel, rel_w, t.rel_off, g.d_rel, t.rel_ld, rel_dim, w.dmod,
+                               g.d_modulus, ra);
+        else
+            hipLaunchKernelGGL(bwd_rel_kernel<false>, dim3((unsigned)rb), dim3(kRelWaves * kWave), 0, st, b.pos, B,
+                               t.nrelation, w.qg_rel, rel_w, t.rel_off, g.d_rel, t.rel_ld, rel_dim, w.dmod,
+                               g.d_modulus, ra);
     }
     return check_launch("kge_step_backward");
 }
@@ -2420,8 +2462,38 @@ int64_t kge_train_step_reg_workspace_size(int fn, int64_t nentity, int64_t nrela
     return reg_ws_layout(nullptr, base, nentity, nrelation, rel_ld).bytes;
 }
 
-// kge_train_step (reg_entry false: weights required, no regulariser, no log, its own workspace size) and
-// kge_train_step_reg in one body. Every rejection comes before the first launch.
+// kge_train_step_lazy's workspace: kge_train_step_reg's, then the touched rows' list (min(E, events) ints: a batch
+// touches no more rows than it has events), its count and the 4096-entity tiles' counts
+struct LazyWs {
+    int *list, *count, *tiles;
+    int64_t bytes;
+};
+
+static LazyWs lazy_ws_layout(char* base, int64_t reg_bytes, int64_t E, int64_t B, int64_t N) {
+    LazyWs l;
+    int64_t o = reg_bytes;
+    auto take = [&](int64_t bytes) {
+        char* p = base ? base + o : nullptr;
+        o += align256(bytes);
+        return (int*)p;
+    };
+    l.list = take(std::min<int64_t>(E, B * N + 3 * B) * 4);
+    l.count = take(4);
+    l.tiles = take((E + kTile4k - 1) / kTile4k * 4);
+    l.bytes = o;
+    return l;
+}
+
+int64_t kge_train_step_lazy_workspace_size(int fn, int64_t nentity, int64_t nrelation, int64_t rel_ld, int64_t B,
+                                           int64_t N, int64_t D) {
+    const int64_t base = kge_train_step_reg_workspace_size(fn, nentity, nrelation, rel_ld, B, N, D);
+    if (base < 0) return -1;
+    return lazy_ws_layout(nullptr, base, nentity, B, N).bytes;
+}
+
+// kge_train_step (reg_entry false: weights required, no regulariser, no log, its own workspace size),
+// kge_train_step_reg and kge_train_step_lazy (reg_entry with lambda 0, and `lazy`: Adam on the touched rows only)
+// in one body. Every rejection comes before the first launch.
 static int train_step_impl(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld, float* rel,
                            int64_t nrelation, int64_t rel_ld, int64_t rel_off, const int64_t* pos, const int64_t* neg,
                            int64_t neg_ld, int64_t B, int64_t N, int64_t D, float gamma, float emb_range,
@@ -2429,7 +2501,7 @@ static int train_step_impl(int fn, int mode, float* ent, int64_t nentity, int64_
                            float* loss_sum, float* out_neg, float* out_pos, float* m_ent, float* v_ent, float* m_rel,
                            float* v_rel, float lr, float beta1, float beta2, float eps, int64_t step, int keras,
                            void* workspace, int64_t workspace_bytes, void* stream, bool reg_entry,
-                           float regularization, float* log) {
+                           float regularization, float* log, bool lazy = false) {
     int rc = check_fn_mode(fn, mode);
     if (rc) return rc;
     if (fn == KGE_PROTATE) return fail(KGE_ENOTSUP, "kge_train_step: pRotatE uses kge_step_backward_adam");
@@ -2445,7 +2517,8 @@ static int train_step_impl(int fn, int mode, float* ent, int64_t nentity, int64_
         return fail(KGE_EINVAL, "too many gradient events for 32-bit codes");
     const TrainWs t = train_ws_layout((char*)workspace, fn, nentity, nrelation, rel_ld, B, N, D);
     const RegWs rw = reg_ws_layout((char*)workspace, t.bytes, nentity, nrelation, rel_ld);
-    if (!workspace || workspace_bytes < (reg_entry ? rw.bytes : t.bytes))
+    const LazyWs lw = lazy_ws_layout((char*)workspace, rw.bytes, nentity, B, N);
+    if (!workspace || workspace_bytes < (lazy ? lw.bytes : reg_entry ? rw.bytes : t.bytes))
         return fail(KGE_EINVAL, "workspace too small");
     // the finishing launch of the regulariser's value and the log; without it (kge_train_step; lambda 0 and no
     // log) the step is launch for launch the plain one
@@ -2468,6 +2541,10 @@ static int train_step_impl(int fn, int mode, float* ent, int64_t nentity, int64_
     o.loss = loss;
     o.loss_sum = loss_sum;  // with the finishing launch, the Sum metric advances there, by the loss with its term
     o.log = log;
+    o.lazy = lazy;
+    o.lz_list = lw.list;
+    o.lz_count = lw.count;
+    o.lz_tiles = lw.tiles;
     float* const parts = reg_finish ? rw.loss_parts : nullptr;
     float* const sum_now = reg_finish ? nullptr : loss_sum;
 
@@ -2583,6 +2660,20 @@ int kge_train_step_reg(int fn, int mode, float* ent, int64_t nentity, int64_t en
                            gamma, emb_range, temperature, adversarial, detach, weight, loss, loss_sum, out_neg,
                            out_pos, m_ent, v_ent, m_rel, v_rel, lr, beta1, beta2, eps, step, keras, workspace,
                            workspace_bytes, stream, true, regularization, log);
+}
+
+// kge_train_step with a lazy Adam: only the rows a batch touches are read or written (see kge_hip.h)
+int kge_train_step_lazy(int fn, int mode, float* ent, int64_t nentity, int64_t ent_ld, float* rel, int64_t nrelation,
+                        int64_t rel_ld, int64_t rel_off, const int64_t* pos, const int64_t* neg, int64_t neg_ld,
+                        int64_t B, int64_t N, int64_t D, float gamma, float emb_range, float temperature,
+                        int adversarial, int detach, const float* weight, float* loss, float* loss_sum, float* out_neg,
+                        float* out_pos, float* m_ent, float* v_ent, float* m_rel, float* v_rel, float lr, float beta1,
+                        float beta2, float eps, int64_t step, int keras, void* workspace, int64_t workspace_bytes,
+                        void* stream, float* log) {
+    return train_step_impl(fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, neg, neg_ld, B, N, D,
+                           gamma, emb_range, temperature, adversarial, detach, weight, loss, loss_sum, out_neg,
+                           out_pos, m_ent, v_ent, m_rel, v_rel, lr, beta1, beta2, eps, step, keras, workspace,
+                           workspace_bytes, stream, true, 0.f, log, true);
 }
 
 }  // extern "C"

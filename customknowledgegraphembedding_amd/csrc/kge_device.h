@@ -3015,9 +3015,17 @@ __device__ __forceinline__ void ent_event(const ScoreParams& p, const Cand<FN, V
 // REG: the L3 regulariser of kge_train_step_reg (p.reg3 != 0) joins the fused optimizer; a template parameter, so
 // the plain instances are the code they were (as a runtime branch it cost them 1-16 VGPRs,
 // profiles/r09_train_reg_resources.txt)
-template <int FN, bool CH, int V, int G, bool REG = false>
+// LAZY: the lazy Adam of kge_train_step_lazy. Wave i takes row p.lz_list[i] of the touched rows' list instead of row
+// i and leaves past the list's count; everything after the row index is the one code. A template parameter for
+// REG's reason: the plain instances are the code they were (profiles/r18_lazy_adam_resources.txt).
+template <int FN, bool CH, int V, int G, bool REG = false, bool LAZY = false>
 __global__ __launch_bounds__(kBlock) void bwd_ent_kernel(ScoreParams p) {
-    const int64_t e = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    int64_t e = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if constexpr (LAZY) {
+        if (e >= min((int64_t)*p.lz_count, p.lz_rows)) return;
+        e = p.lz_list[e];
+        if (e < 0) return;  // (a stray entry never indexes the table)
+    }
     if (e >= p.c_rows) return;
     const int lane = threadIdx.x & 63;
     const int D = p.D, DV = D / V;
@@ -3548,7 +3556,7 @@ constexpr int kEntSortMax = 2048;
 // the relation row, is read from the relation table instead: it stays in L2)
 constexpr int ent_nq(int fn) { return (fn == KGE_COMPLEX || fn == KGE_ROTATE || fn == KGE_INTERHT) ? 2 : 1; }
 
-template <int FN, bool CH, int V, int G, bool REG = false>  // REG: as bwd_ent_kernel's
+template <int FN, bool CH, int V, int G, bool REG = false, bool LAZY = false>  // REG, LAZY: as bwd_ent_kernel's
 __global__ __launch_bounds__(kBlock) void bwd_ent_stream_kernel(ScoreParams p) {
     static_assert(G % kWavesPerBlock == 0, "the streaming phase 2 needs a multiple of 4 groups per lane");
     constexpr int GW = G / kWavesPerBlock;
@@ -3559,7 +3567,12 @@ __global__ __launch_bounds__(kBlock) void bwd_ent_stream_kernel(ScoreParams p) {
     constexpr int NQ = ent_nq(FN);
     __shared__ float red[2][kWavesPerBlock];
     __shared__ int srt[kEntSortMax];  // a large bucket's codes, sorted block-wide
-    const int64_t e = blockIdx.x;
+    int64_t e = blockIdx.x;
+    if constexpr (LAZY) {  // block-uniform: block i takes the i-th touched row
+        if (e >= min((int64_t)*p.lz_count, p.lz_rows)) return;
+        e = p.lz_list[e];
+        if (e < 0) return;
+    }
     if (e >= p.c_rows) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int D = p.D, DV = D / V;
@@ -4199,11 +4212,19 @@ void launch_tile(const ScoreParams& p, hipStream_t st, int blocks) {
         }                                              \
         return false;                                  \
     }
-// phase 2: the plain instance, or the one with the L3 regulariser (kge_train_step_reg with lambda != 0; it refuses
-// pRotatE, which has no such instance)
+// phase 2: the plain instance, the one with the L3 regulariser (kge_train_step_reg with lambda != 0; it refuses
+// pRotatE, which has no such instance), or the lazy one (kge_train_step_lazy: p.lz_list; no pRotatE, no regulariser)
 #define KGE_KIND_REG(K, kernel)                        \
     if (kind == K) {                                   \
         if constexpr (kind_has(K, FN, CH, G)) {        \
+            if (p.lz_list) {                           \
+                if constexpr (FN != KGE_PROTATE) {     \
+                    if (p.reg3 != 0.f) return false;   \
+                    KGE_LAUNCH(kernel, FN, CH, V, G, false, true); \
+                    return true;                       \
+                }                                      \
+                return false;                          \
+            }                                          \
             if (p.reg3 == 0.f) {                       \
                 KGE_LAUNCH(kernel, FN, CH, V, G);      \
                 return true;                           \

@@ -352,6 +352,10 @@ struct ScoreParams {
     // L3 ("N3") regulariser in phase 2 (kge_train_step_reg). reg3 == 0: off, the plain instances run.
     float reg3;       // 3 lambda: every element x of row e gets reg3 x |x| added to its gradient before Adam
     float* reg_part;  // sum |x|^3 of what each wave holds: [E] (bwd_ent_kernel), [E, 4] (bwd_ent_stream_kernel)
+    // lazy Adam in phase 2 (kge_train_step_lazy). lz_list null: off, every row is visited (the plain instances run).
+    const int* lz_list;   // [lz_rows] the rows with events, ascending (lazy_list_kernel)
+    const int* lz_count;  // [1] how many of them the list holds
+    int64_t lz_rows;      // the list's size, min(E, events): block (or wave) i of the LAZY instances takes lz_list[i]
 };
 // the wave count whose planned instances exist with the plan-sharing loop (SHARED: the row rule's shapes run 12 waves)
 constexpr int kTileSharedWaves = 12;

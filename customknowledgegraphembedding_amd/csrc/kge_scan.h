@@ -205,5 +205,83 @@ __global__ __launch_bounds__(kScanTile) __attribute__((unused)) void scan_tiles4
     if (t == 0) tile_sum[blockIdx.x] = all;
 }
 
+// The touched rows of the lazy train step (kge_train_step_lazy): the entities whose bucket holds an event, ascending,
+// and how many there are. Two launches behind the scan, on the GLOBAL offsets off[0..E] that phase 2 reads (so
+// both scan paths and the separate-phase-1 fallback feed it the same thing): lazy_count_kernel leaves each
+// 4096-entity tile's number of touched rows, lazy_list_kernel adds up the tiles before its own (integer sums: any
+// order gives the same value), scans its tile and writes the rows. Everything it reads is written earlier in the
+// same call and every int it leaves is overwritten by the next, so the workspace carries no state. A row is
+// touched by phase 2's own test: the clamped bucket is not empty.
+__device__ __forceinline__ int lazy_touched(const int* __restrict__ off, int64_t e, int ntot) {
+    const int lo = min(max(off[e], 0), ntot), hi = min(max(off[e + 1], lo), ntot);
+    return hi > lo ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kScanTile) __attribute__((unused)) void lazy_count_kernel(const int* __restrict__ off, int64_t E, int ntot,
+                                                               int* __restrict__ tile_cnt) {
+    constexpr int NW = kScanTile / kWave;
+    __shared__ int wtot[NW];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t e0 = (int64_t)blockIdx.x * kTile4k + (int64_t)t * 4;
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (e0 + j < E) c += lazy_touched(off, e0 + j, ntot);
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) c += __shfl_xor(c, o, kWave);
+    if (lane == 0) wtot[w] = c;
+    __syncthreads();
+    if (t == 0) {
+        int all = 0;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) all += wtot[ww];
+        tile_cnt[blockIdx.x] = all;
+    }
+}
+
+// list[0..count): the touched rows, ascending; count <= cap (the caller's bound, min(E, events): the list's size)
+__global__ __launch_bounds__(kScanTile) __attribute__((unused)) void lazy_list_kernel(const int* __restrict__ off, int64_t E, int ntot,
+                                                              const int* __restrict__ tile_cnt, int* __restrict__ list,
+                                                              int cap, int* __restrict__ count) {
+    constexpr int NW = kScanTile / kWave;
+    __shared__ int wpre[NW], wtot[NW];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    int pre = 0;  // touched rows of the tiles before this one
+    for (int i = t; i < (int)blockIdx.x; i += kScanTile) pre += tile_cnt[i];
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) pre += __shfl_xor(pre, o, kWave);
+    const int64_t e0 = (int64_t)blockIdx.x * kTile4k + (int64_t)t * 4;
+    int f[4], c = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        f[j] = e0 + j < E ? lazy_touched(off, e0 + j, ntot) : 0;
+        c += f[j];
+    }
+    int incl = c;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const int y = __shfl_up(incl, o, kWave);
+        if (lane >= o) incl += y;
+    }
+    if (lane == 0) wpre[w] = pre;
+    if (lane == kWave - 1) wtot[w] = incl;
+    __syncthreads();
+    int base = 0, before = 0, all = 0;
+#pragma unroll
+    for (int ww = 0; ww < NW; ++ww) {
+        base += wpre[ww];
+        before += ww < w ? wtot[ww] : 0;
+        all += wtot[ww];
+    }
+    int run = base + before + incl - c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (f[j]) {
+            if (run >= 0 && run < cap) list[run] = (int)(e0 + j);
+            ++run;
+        }
+    if (blockIdx.x == gridDim.x - 1 && t == 0) *count = min(max(base + all, 0), cap);
+}
+
 }  // namespace
 }  // namespace kge_impl

@@ -286,6 +286,11 @@ class TFKGEModel(_KGEBase):
             raise TypeError("train_step_fused needs customknowledgegraphembedding_amd.optim.Adam")
         if not self.supports_fused_step:
             raise NotImplementedError(f"{self.model_name} has no fused train step; use the autograd path")
+        lazy = _lazy_group(optimizer)
+        if lazy and self.model_name == "pRotatE":
+            raise NotImplementedError("pRotatE has no lazy train step (kge_train_step_lazy)")
+        if lazy and not one_call:
+            raise ValueError("a lazy Adam needs the one-call train step (one_call=True)")
         m = ops.mode_id(mode)
         fn = FN_IDS[self.model_name]
         ent, rel = self.entity_embedding, self.relation_embedding
@@ -297,7 +302,7 @@ class TFKGEModel(_KGEBase):
                 check_adam_moments(prm, optimizer.state[prm])
         if one_call and not is_p:
             return self._train_step_one_call(fn, m, positive_sample, negative_sample, subsampling_weight, optimizer,
-                                             loss_sum)
+                                             loss_sum, lazy)
         if loss_sum is not None:
             loss = self.train_step_fused(positive_sample, negative_sample, subsampling_weight, mode, optimizer,
                                          one_call=False)
@@ -335,8 +340,8 @@ class TFKGEModel(_KGEBase):
         return loss.detach()
 
     def _train_step_one_call(self, fn, m, positive_sample, negative_sample, subsampling_weight, optimizer,
-                             loss_sum=None):
-        """kge_train_step: supervisor.py:15-26 in one C-ABI call."""
+                             loss_sum=None, lazy=False):
+        """kge_train_step (a lazy Adam group: kge_train_step_lazy): supervisor.py:15-26 in one C-ABI call."""
         from . import _lib
 
         ent, rel = self.entity_embedding, self.relation_embedding
@@ -353,10 +358,13 @@ class TFKGEModel(_KGEBase):
         group, lr, step = self._adam_state(optimizer, [ent, rel])
         b1, b2 = group["betas"]
         lib = _lib.load()
-        nbytes = lib.kge_train_step_workspace_size(fn, ent.shape[0], rel.shape[0], rel.stride(0), B, N, self._D)
+        size_fn, step_fn, name = lib.kge_train_step_workspace_size, lib.kge_train_step, "kge_train_step"
+        if lazy:
+            size_fn, step_fn, name = lib.kge_train_step_lazy_workspace_size, lib.kge_train_step_lazy, name + "_lazy"
+        nbytes = size_fn(fn, ent.shape[0], rel.shape[0], rel.stride(0), B, N, self._D)
         ws = self._train_workspace(nbytes, dev)
         out = torch.empty(2 * B + 1, dtype=torch.float32, device=dev)  # loss | out_neg | out_pos
-        rc = lib.kge_train_step(
+        rc = step_fn(
             fn, m, ent.data_ptr(), ent.shape[0], ent.stride(0), rel.data_ptr(), rel.shape[0], rel.stride(0),
             self._rel_off, pos.data_ptr(), neg.data_ptr(), neg.stride(0), B, N, self._D, self._gamma_f,
             self._range_f, 1.0, 1, 0, w.data_ptr(), out.data_ptr(),
@@ -364,8 +372,8 @@ class TFKGEModel(_KGEBase):
             optimizer.state[ent]["exp_avg"].data_ptr(), optimizer.state[ent]["exp_avg_sq"].data_ptr(),
             optimizer.state[rel]["exp_avg"].data_ptr(), optimizer.state[rel]["exp_avg_sq"].data_ptr(),
             float(lr), float(b1), float(b2), float(group["eps"]), int(step), int(group["semantics"] == "keras"),
-            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, "kge_train_step")
+            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream, *((None,) if lazy else ()))
+        _lib.check(rc, name)
         self._adam_commit(optimizer, [ent, rel])
         return out[0]
 
@@ -476,6 +484,10 @@ class KGEModel(_KGEBase):
             raise TypeError("train_step_fused needs customknowledgegraphembedding_amd.optim.Adam")
         if model.model_name == "pRotatE":
             raise NotImplementedError("pRotatE has no fused train step (kge_train_step_reg); use KGEModel.train_step")
+        lazy = _lazy_group(optimizer)
+        if lazy and float(args.regularization) != 0.0:
+            raise ValueError("a lazy Adam cannot take the L3 regulariser: its gradient is dense "
+                             "(regularization must be 0)")
         model.train()
         positive_sample, negative_sample, subsampling_weight, mode = next(train_iterator)
         ent, rel = model.entity_embedding, model.relation_embedding
@@ -499,10 +511,14 @@ class KGEModel(_KGEBase):
         group, lr, step = model._adam_state(optimizer, [ent, rel])
         b1, b2 = group["betas"]
         lib = _lib.load()
-        nbytes = lib.kge_train_step_reg_workspace_size(fn, ent.shape[0], rel.shape[0], rel.stride(0), B, N, model._D)
+        size_fn, step_fn, name = lib.kge_train_step_reg_workspace_size, lib.kge_train_step_reg, "kge_train_step_reg"
+        if lazy:
+            size_fn, step_fn = lib.kge_train_step_lazy_workspace_size, lib.kge_train_step_lazy
+            name = "kge_train_step_lazy"
+        nbytes = size_fn(fn, ent.shape[0], rel.shape[0], rel.stride(0), B, N, model._D)
         ws = model._train_workspace(nbytes, dev)
         out = torch.empty(2 * B + 5, dtype=torch.float32, device=dev)  # log[4] | loss | out_neg | out_pos
-        rc = lib.kge_train_step_reg(
+        rc = step_fn(
             fn, m, ent.data_ptr(), ent.shape[0], ent.stride(0), rel.data_ptr(), rel.shape[0], rel.stride(0),
             model._rel_off, pos.data_ptr(), neg.data_ptr(), neg.stride(0), B, N, model._D, model._gamma_f,
             model._range_f, temp, int(adv), 1, None if w is None else w.data_ptr(), out[4:].data_ptr(), None,
@@ -510,13 +526,19 @@ class KGEModel(_KGEBase):
             optimizer.state[ent]["exp_avg"].data_ptr(), optimizer.state[ent]["exp_avg_sq"].data_ptr(),
             optimizer.state[rel]["exp_avg"].data_ptr(), optimizer.state[rel]["exp_avg_sq"].data_ptr(),
             float(lr), float(b1), float(b2), float(group["eps"]), int(step), int(group["semantics"] == "keras"),
-            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream, reg, out.data_ptr())
-        _lib.check(rc, "kge_train_step_reg")
+            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream,
+            *((out.data_ptr(),) if lazy else (reg, out.data_ptr())))
+        _lib.check(rc, name)
         model._adam_commit(optimizer, [ent, rel])
         loss, pos_loss, neg_loss, reg_term = out[:4].tolist()
         log = {"regularization": reg_term} if reg != 0.0 else {}
         log.update(positive_sample_loss=pos_loss, negative_sample_loss=neg_loss, loss=loss)
         return log
+
+
+def _lazy_group(optimizer):
+    """Whether the optimizer's group asks for the lazy Adam (optim.Adam(..., lazy=True))."""
+    return bool(optimizer.param_groups[0].get("lazy", False))
 
 
 def default_hidden_range(gamma, hidden_dim, epsilon=2.0):

@@ -3,6 +3,11 @@ step (supervisor.py:26 `optimizer.apply_gradients`; run.py:111 `tf.keras.optimiz
 
 semantics="keras" (default, the TF reference): eps=1e-7 added to sqrt(v), bias correction folded
 into the step size; semantics="torch": torch.optim.Adam's update (eps added to sqrt(v_hat)).
+
+lazy=True: only the rows a batch touches are updated; the moments of the others do not decay (TF-addons
+LazyAdam; with semantics="keras" and eps=1e-8, torch.optim.SparseAdam). A knowingly changed semantic
+(DESIGN §6), and one only the fused train step can apply (kge_train_step_lazy, train_step_fused): a dense
+.grad does not say which rows were touched, so step() refuses a lazy group.
 """
 from __future__ import annotations
 
@@ -50,15 +55,18 @@ def resolve_lr(lr, iterations):
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=None, semantics="keras"):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=None, semantics="keras", lazy=False):
         if semantics not in ("keras", "torch"):
             raise ValueError("semantics must be 'keras' or 'torch'")
         if eps is None:
             eps = 1e-7 if semantics == "keras" else 1e-8
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, semantics=semantics))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, semantics=semantics, lazy=bool(lazy)))
 
     @torch.no_grad()
     def step(self, closure=None):
+        if any(group.get("lazy", False) for group in self.param_groups):
+            raise NotImplementedError("a lazy Adam group is updated by train_step_fused (kge_train_step_lazy): a "
+                                      "dense .grad does not say which rows a batch touched")
         loss = None
         if closure is not None:
             with torch.enable_grad():

@@ -95,6 +95,9 @@ class Trainer:
         self.metrics = metrics
         self.strategy = strategy
         replicas = strategy.num_replicas_in_sync
+        if replicas > 1 and any(g.get("lazy", False) for g in getattr(optimizer, "param_groups", [])):
+            # the row-sharded step and the dense all-reduce path both apply the dense Adam
+            raise NotImplementedError("a lazy Adam (optim.Adam(lazy=True)) is single-replica only")
         if fused is None:
             # the fused optimizer never materialises gradients: it needs this package's Adam over
             # exactly the model's parameters in one group (and, across replicas, no pRotatE modulus)

@@ -11,7 +11,8 @@ Build with the remarks on and keep the log, then name the kernels:
 (-O keeps each unit's remarks together: interleaved remarks of parallel units cannot be told apart.)
 
 One line per instance: kernel, template arguments as mangled (FN, CH, V, G, ...), VGPRs, AGPRs, scratch bytes per
-lane, spilled VGPRs, static LDS bytes (dynamic LDS is the launch's and not in the remarks), waves per SIMD. Exits 1
+lane, spilled VGPRs, static LDS bytes (dynamic LDS is the launch's and not in the remarks), waves per SIMD, and with
+--sgprs the total SGPRs. Exits 1
 when an instance with G <= 4 has scratch or spills (--max-g changes the bound)."""
 import argparse
 import re
@@ -48,10 +49,12 @@ def main():
     ap.add_argument("log")
     ap.add_argument("kernels", nargs="+")
     ap.add_argument("--max-g", type=int, default=4, help="instances up to this G must not spill")
+    ap.add_argument("--sgprs", action="store_true", help="a last column with the total SGPRs")
     a = ap.parse_args()
     res = parse(a.log)
     bad = 0
-    print("kernel fn ch V G rest | VGPRs AGPRs scratch_B/lane vgpr_spill static_LDS_B waves/SIMD")
+    print("kernel fn ch V G rest | VGPRs AGPRs scratch_B/lane vgpr_spill static_LDS_B waves/SIMD"
+          + (" SGPRs" if a.sgprs else ""))
     rows = []
     for mangled, f in res.items():
         for k in a.kernels:
@@ -67,7 +70,7 @@ def main():
             flag = "  <-- spills"
         print(f"{k} {FN_NAMES.get(fn, fn)} {'head' if ch else 'tail'} V{v} G{g} {t[4:]} | {f.get('VGPRs', -1)} "
               f"{f.get('AGPRs', -1)} {scratch} {spill} {f.get('LDS Size [bytes/block]', -1)} "
-              f"{f.get('Occupancy [waves/SIMD]', -1)}{flag}")
+              f"{f.get('Occupancy [waves/SIMD]', -1)}{' %d' % f.get('TotalSGPRs', -1) if a.sgprs else ''}{flag}")
     print(f"{len(rows)} instances, {bad} spilling at G <= {a.max_g}")
     return 1 if bad or not rows else 0
 
