@@ -174,6 +174,11 @@ SIGNATURES = {
     "kge_eval_rank_sweep_workspace_size": (_c_i64, [_c_i64, _c_i64]),
     "kge_eval_rank_sweep": (_c_i, [_c_i, _c_i, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_i64,
                                    _c_f, _c_f, _c_f, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    # (fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, M, D, gamma, emb_range, modulus, truth,
+    #  cand, cand_ld, C, filter_ptr, filter_ids, nfilter, ranks, ties, truth_scores, stream)
+    "kge_eval_rank_candidates": (_c_i, [_c_i, _c_i, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64,
+                                        _c_i64, _c_f, _c_f, _c_f, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p,
+                                        _c_p, _c_p, _c_p]),
     "kge_eval_topk_sweep_workspace_size": (_c_i64, [_c_i64, _c_i64]),
     # (fn, mode, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, pos, B, D, gamma, emb_range, modulus,
     #  excl_ptr, excl_ids, nexcl, k, out_ids, ids_ld, out_scores, scores_ld, workspace, workspace_bytes, stream)

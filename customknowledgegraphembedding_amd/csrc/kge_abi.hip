@@ -571,7 +571,8 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
     int rc = check_fn_mode(fn, mode);
     if (rc) return rc;
     if (p.B < 0 || p.N < 0 || p.D <= 0) return fail(KGE_EINVAL, "bad shape (B, N, D)");
-    if (p.B == 0 || p.N == 0) return ok();
+    // (an empty candidate list still ranks: kge_eval_rank_candidates writes rank 1 for every row)
+    if (p.B == 0 || (p.N == 0 && kind != KIND_RANK_CAND)) return ok();
     // a rank of the sharded train step that owns no rows has no shard to point at: nothing reads p.cent then
     const bool no_rows =
         p.c_rows == 0 && (kind == KIND_SHARD_FWD_GRAD || kind == KIND_SHARD_POS || kind == KIND_SHARD_EPILOGUE);
@@ -644,6 +645,12 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
                 return fail(KGE_EINVAL, "sweep plan missing");
             waves = (p.B + p.tile_rows - 1) / p.tile_rows * 8 * p.tk.chunks * kWavesPerBlock;
             break;
+        case GRID_RANK_CAND: {
+            p.wpr = rank_cand_wpr(p.N);
+            const int64_t rows = kWavesPerBlock / p.wpr;  // query rows per block
+            waves = (p.B + rows - 1) / rows * kWavesPerBlock;
+            break;
+        }
     }
     const int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > INT32_MAX) return fail(KGE_EINVAL, "problem too large for one launch");
@@ -1782,6 +1789,45 @@ int kge_eval_rank_sweep(int fn, int mode, const float* ent, int64_t nentity, int
     if (rc) return rc;
     launch_rank_finish(B, nentity, truth, filter_ptr, filter_ids, workspace, ranks, (hipStream_t)stream);
     return check_launch("kge_eval_rank_sweep");
+}
+
+int kge_eval_rank_candidates(int fn, int mode, const float* ent, int64_t nentity, int64_t ent_ld, const float* rel,
+                             int64_t nrelation, int64_t rel_ld, int64_t rel_off, const int64_t* pos, int64_t M,
+                             int64_t D, float gamma, float emb_range, float modulus, const int64_t* truth,
+                             const int64_t* cand, int64_t cand_ld, int64_t C, const int64_t* filter_ptr,
+                             const int64_t* filter_ids, int64_t nfilter, int64_t* ranks, int64_t* ties,
+                             float* truth_scores, void* stream) {
+    if (!valid_fn(fn)) return fail(KGE_EINVAL, "unknown score function id " + std::to_string(fn));
+    if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH)
+        return fail(KGE_EINVAL, "kge_eval_rank_candidates: mode must be 0 (head-batch) or 1 (tail-batch)");
+    if (M < 0 || C < 0 || D <= 0 || nentity < 0 || nrelation < 0 || nfilter < 0 || cand_ld < 0)
+        return fail(KGE_EINVAL, "kge_eval_rank_candidates: bad shape");
+    if (cand_ld > 0 && cand_ld < C)
+        return fail(KGE_EINVAL, "kge_eval_rank_candidates: cand_ld must be 0 (one shared list) or >= C");
+    if (M == 0) return ok();
+    if (!ent || !rel || !pos || !truth || !ranks) return fail(KGE_EINVAL, "kge_eval_rank_candidates: null pointer");
+    if (C > 0 && !cand) return fail(KGE_EINVAL, "kge_eval_rank_candidates: cand must not be NULL with C > 0");
+    if (nfilter > 0 && (!filter_ptr || !filter_ids))
+        return fail(KGE_EINVAL, "kge_eval_rank_candidates: null filter pointer with nfilter > 0");
+    const Tables t = {fn, ent, nentity, ent_ld, rel, nrelation, rel_ld, rel_off, D, gamma, emb_range, modulus};
+    if (nfilter == 0) filter_ptr = filter_ids = nullptr;
+    // a launch takes at most kRows query rows (a block per row at the widest); more rows are further launches
+    constexpr int64_t kRows = (int64_t)1 << 30;
+    for (int64_t r0 = 0; r0 < M; r0 += kRows) {
+        const int64_t n = std::min(kRows, M - r0);
+        ScoreParams p;
+        fill_indexed(p, t, {mode, pos + 3 * r0, cand ? cand + r0 * cand_ld : nullptr, cand_ld, n, C});
+        p.rk.truth = truth + r0;
+        p.rk.fptr = filter_ptr ? filter_ptr + r0 : nullptr;  // the starts are offsets into filter_ids: no rebase
+        p.rk.fids = filter_ids;
+        p.rk.nf = nfilter;
+        p.rk.ts = truth_scores ? truth_scores + r0 : nullptr;
+        p.rc.ranks = ranks + r0;
+        p.rc.ties = ties ? ties + r0 : nullptr;
+        const int rc = run_score(fn, mode, p, KIND_RANK_CAND, stream);  // refuses a width as kge_score_indexed does
+        if (rc) return rc;
+    }
+    return ok();
 }
 
 int64_t kge_eval_topk_sweep_workspace_size(int64_t B, int64_t k) {

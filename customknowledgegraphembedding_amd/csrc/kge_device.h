@@ -4153,6 +4153,71 @@ __global__ __launch_bounds__(NWV * kWave) void topk_sweep_kernel(ScoreParams p) 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ranks against a given candidate list per query row (kge_eval_rank_candidates), one launch, no workspace, no
+// atomics. p.wpr (1, 2 or 4: rank_cand_wpr) waves take a query row, kWavesPerBlock / p.wpr rows a block. Every wave
+// builds its row's query (build_query_for) and scores the row's truth itself (cand_score: one more gather of a row
+// its sibling waves touch too, and no barrier before the counting), then takes the runs of 64 list entries wi,
+// wi + wpr, ... through score_lanes (entry j's score in lane j: bitwise the element kge_score_indexed writes).
+// Lane j decides whether its entry is counted: an id in [0, c_rows), not the truth, not among the row's ascending
+// filter ids (a binary search per lane; the ids are read one by one, the slices being 8-B aligned only). Every
+// entry adds 0 or 1, so a ballot's popcount is the run's count: above and ties are wave-uniform and need no
+// reduction. The row's waves are summed through 2 LDS ints per wave; the row's first wave writes its outputs.
+// ---------------------------------------------------------------------------------------------
+template <int FN, bool CH, int V, int G>
+__global__ __launch_bounds__(kBlock) void rank_cand_kernel(ScoreParams p) {
+    __shared__ int red[kWavesPerBlock][2];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int wpr = p.wpr;  // a power of two <= kWavesPerBlock
+    const int wi = w & (wpr - 1);
+    const int64_t b = (int64_t)blockIdx.x * (kWavesPerBlock / wpr) + (w / wpr);
+    const bool live = b < p.B;  // wave-uniform; a dead wave still meets the block's barrier
+    int above = 0, ties = 0;
+    float ts = -INFINITY;
+    if (live) {
+        Query<FN, CH, V, G> q;
+        int64_t qi, ri;
+        bool qok, rok, tok;
+        build_query_for<FN, CH, V, G>(p, b, lane, q, qi, ri, qok, rok);
+        const int64_t truth = p.rk.truth[b];
+        {
+            Cand<FN, V, G> c;
+            c.load(cand_row(p, truth, tok), tok, p.D, lane);
+            const float s = cand_score<FN, CH, V, G>(c, q, p);
+            ts = tok ? s : -INFINITY;  // kge_eval_rank_sweep's score of an out-of-range truth
+        }
+        const int64_t flo = p.rk.fptr ? p.rk.fptr[b] : 0, fhi = p.rk.fptr ? p.rk.fptr[b + 1] : 0;
+        const int64_t* ids = p.c_idx + b * p.c_stride;
+        for (int64_t n0 = (int64_t)wi * kWave; n0 < p.N; n0 += (int64_t)wpr * kWave) {
+            const int nc = (int)min((int64_t)kWave, p.N - n0);
+            const int64_t my_id = lane < nc ? ids[n0 + lane] : -1;
+            float2 unused;
+            const float s = score_lanes<FN, CH, V, G, false>(p, q, my_id, nc, lane, unused);
+            bool counted = lane < nc && my_id >= 0 && my_id < p.c_rows && my_id != truth;
+            if (counted && fhi > flo) counted = !topk_listed(p.rk.fids, flo, fhi, my_id);
+            above += __popcll(__ballot(counted && s > ts));  // strict >: a NaN on either side never counts
+            ties += __popcll(__ballot(counted && s == ts));
+        }
+    }
+    if (wpr > 1) {  // block-uniform
+        if (lane == 0) {
+            red[w][0] = above;
+            red[w][1] = ties;
+        }
+        __syncthreads();
+        if (wi != 0) return;
+        for (int k = 1; k < wpr; ++k) {
+            above += red[w + k][0];
+            ties += red[w + k][1];
+        }
+    }
+    if (live && lane == 0) {
+        p.rc.ranks[b] = 1 + (int64_t)above;
+        if (p.rc.ties) p.rc.ties[b] = ties;
+        if (p.rk.ts) p.rk.ts[b] = ts;
+    }
+}
+
 }  // namespace kge_impl
 
 #include "kge_shard.h"
@@ -4290,6 +4355,7 @@ bool launch_one(const ScoreParams& p, int kind, hipStream_t st, int blocks) {
         }
         return false;
     }
+    KGE_KIND(KIND_RANK_CAND, rank_cand_kernel, FN, CH, V, G)
     KGE_KIND(KIND_SCORE_SHARD_XCD, score_sharded_xcd_kernel, FN, CH, V, G)
     KGE_KIND(KIND_SHARD_BUCKET, shard_bucket_kernel, FN, CH, V, G)
     if (kind == KIND_STEP_FWD_GRAD) {

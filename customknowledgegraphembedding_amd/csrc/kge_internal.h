@@ -40,6 +40,7 @@ enum Kind {
     KIND_RANK_PAIRS = 21,      // kge_eval_rank_sweep: the truths' and the filter entries' scores (one wave per pair)
     KIND_RANK_SWEEP = 22,      // kge_eval_rank_sweep: every entity row against a group of query rows, counting
     KIND_TOPK_SWEEP = 23,      // kge_eval_topk_sweep: the same sweep, each wave keeping the best k per query row
+    KIND_RANK_CAND = 24,       // kge_eval_rank_candidates: each query row against its own candidate list, counting
     KIND_COUNT
 };
 constexpr int kFwdGradMaxG = 4;  // the fused forward + query gradient keeps 6 accumulators per element
@@ -83,7 +84,11 @@ enum GridRule {
     GRID_RANK_PAIRS,          // a wave per pair: B truths, then p.rk.nf filter entries
     GRID_RANK_SWEEP,          // a block per (group of p.tile_rows rows, entity slice, chunk of p.rk.chunks)
     GRID_TOPK_SWEEP,          // the same with p.tk.chunks chunks
+    GRID_RANK_CAND,           // p.wpr = rank_cand_wpr(N) waves per row: ceil(B / (kWavesPerBlock / p.wpr)) blocks
 };
+// rank_cand_kernel: waves per query row, min(4, ceil(C / 64)) rounded up to a power of two (a list of up to 64
+// entries takes one wave, so four rows share a block and none of its waves idles)
+constexpr int rank_cand_wpr(int64_t C) { return C <= kWave ? 1 : (C <= 2 * kWave ? 2 : kWavesPerBlock); }
 
 // What a kind needs, stated once: run_score checks a launch against its entry and launch_one / launch_shard
 // take their `if constexpr` guards from the same entry (kind_has), so the host check and the set of
@@ -124,6 +129,7 @@ constexpr KindInfo kKinds[KIND_COUNT] = {
     /* KIND_RANK_PAIRS */      {GRID_RANK_PAIRS, true, kSweepMaxG, false, false, false, "kge_eval_rank_sweep", true},
     /* KIND_RANK_SWEEP */      {GRID_RANK_SWEEP, true, kSweepMaxG, false, false, false, "kge_eval_rank_sweep", true},
     /* KIND_TOPK_SWEEP */      {GRID_TOPK_SWEEP, true, kSweepMaxG, false, false, false, "kge_eval_topk_sweep", true},
+    /* KIND_RANK_CAND */       {GRID_RANK_CAND, true, kMaxG, false, false, false, "kge_eval_rank_candidates"},
 };
 // whether kind k has a (FN, CH, G) instantiation
 constexpr bool kind_has(int k, int fn, bool ch, int G) {
@@ -356,6 +362,12 @@ struct ScoreParams {
     const int* lz_list;   // [lz_rows] the rows with events, ascending (lazy_list_kernel)
     const int* lz_count;  // [1] how many of them the list holds
     int64_t lz_rows;      // the list's size, min(E, events): block (or wave) i of the LAZY instances takes lz_list[i]
+    // kge_eval_rank_candidates (rank_cand_kernel; the lists are c_idx / c_stride / N, the truths and the filter CSR
+    // rk.truth / rk.fptr / rk.fids, the truths' scores rk.ts, which may be null here)
+    struct {
+        int64_t* ranks;  // [B] 1 + counted entries above the truth
+        int64_t* ties;   // [B] counted entries equal to the truth, or null
+    } rc;
 };
 // the wave count whose planned instances exist with the plan-sharing loop (SHARED: the row rule's shapes run 12 waves)
 constexpr int kTileSharedWaves = 12;

@@ -286,6 +286,171 @@ def rank_sweep(model, positive_sample: torch.Tensor, mode: str, truth: torch.Ten
     return ranks
 
 
+def rank_candidates(model, positive_sample: torch.Tensor, mode: str, candidates: torch.Tensor,
+                    truth: torch.Tensor | None = None, filter_ptr: torch.Tensor | None = None,
+                    filter_ids: torch.Tensor | None = None, nfilter: int | None = None, want_ties: bool = False):
+    """Ranks of a query batch against a given candidate list per query (kge_eval_rank_candidates: one launch, no
+    score matrix, no workspace): the protocol of the large-graph benchmarks (ogbl-wikikg2's 500 negatives per test
+    triple and mode) and of validation against sampled candidates. `candidates` is [M, C] (row-contiguous, any row
+    stride >= C) or [C] (one list shared by all queries), int64 on the tables' device; an id outside [0, nentity)
+    is padding (pad ragged lists with -1). An entry is counted unless it is padding, equals the row's truth or is
+    among the row's filter ids (CSR as rank_sweep's: filter_ptr starts at 0, ids ascending within a row, nfilter =
+    filter_ptr[-1], read from the device when not given); rank = 1 + #{counted entries scoring above the truth}
+    (ties in the positive's favour), ties = #{counted entries scoring exactly the truth's score}. `truth` [M]
+    defaults to the positive's head (head-batch) or tail column. Returns ranks [M] int64, or (ranks, ties) with
+    want_ties. None for a model without a function id (TranSparse), as rank_sweep. The index tensors must be
+    int64, contiguous and on the tables' device (ValueError otherwise). There is no CPU fallback."""
+    if model.model_name not in FN_IDS:
+        return None
+    m = ops.mode_id(mode)
+    if m not in (HEAD_BATCH, TAIL_BATCH):
+        raise ValueError("rank_candidates: mode must be 'head-batch' or 'tail-batch'")
+    ent, rel = model.entity_embedding.detach(), model.relation_embedding.detach()
+    dev = ent.device
+    if positive_sample.dim() != 2 or positive_sample.shape[1] != 3:
+        raise ValueError("rank_candidates: positive_sample must be [M, 3]")
+    M, E = positive_sample.shape[0], ent.shape[0]
+    if not torch.is_tensor(candidates) or candidates.dim() not in (1, 2):
+        raise ValueError("rank_candidates: candidates must be a [M, C] or [C] tensor")
+    if candidates.dtype != torch.int64 or candidates.device != dev:
+        raise ValueError(f"rank_candidates: candidates must be a contiguous int64 tensor on {dev}")
+    if candidates.dim() == 1:
+        if not candidates.is_contiguous():
+            raise ValueError(f"rank_candidates: candidates must be a contiguous int64 tensor on {dev}")
+        C, cand_ld = candidates.shape[0], 0
+    else:
+        C = candidates.shape[1]
+        if candidates.shape[0] != M:
+            raise ValueError(f"rank_candidates: candidates has {candidates.shape[0]} rows, expected {M}")
+        shared = M > 1 and candidates.stride(0) == 0  # an expanded [C] list
+        if (C > 1 and candidates.stride(1) != 1) or (M > 1 and not shared and candidates.stride(0) < C):
+            raise ValueError(f"rank_candidates: candidates must be a contiguous int64 tensor on {dev} "
+                             "(rows contiguous, row stride >= C)")
+        cand_ld = 0 if shared else (max(candidates.stride(0), C) if M > 1 else C)
+    if truth is None and positive_sample.dtype == torch.int64:
+        truth = positive_sample[:, 0 if m == HEAD_BATCH else 2].contiguous()
+    if filter_ptr is None:
+        filter_ids = None
+    for name, t, n in (("positive_sample", positive_sample, 3 * M), ("truth", truth, M),
+                       ("filter_ptr", filter_ptr, M + 1), ("filter_ids", filter_ids, None)):
+        if t is None:
+            continue
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"rank_candidates: {name} must be a contiguous int64 tensor on {dev}")
+        if n is not None and t.numel() != n:
+            raise ValueError(f"rank_candidates: {name} has {t.numel()} elements, expected {n}")
+    ops._need_gpu(ent, rel)
+    lib = _lib.load()
+    nf = (int(filter_ptr[-1]) if nfilter is None else int(nfilter)) if filter_ptr is not None else 0
+    if nf > 0 and (filter_ids is None or filter_ids.numel() < nf):
+        raise ValueError("rank_candidates: filter_ids shorter than nfilter")
+    ranks = torch.empty(M, dtype=torch.int64, device=dev)
+    ties = torch.empty(M, dtype=torch.int64, device=dev) if want_ties else None
+    modulus = float(model.modulus.detach().reshape(-1)[0]) if model.model_name == "pRotatE" else 0.0
+    check(lib.kge_eval_rank_candidates(FN_IDS[model.model_name], m, ent.data_ptr(), E, ent.stride(0), rel.data_ptr(),
+                                       rel.shape[0], rel.stride(0), model._rel_off, positive_sample.data_ptr(), M,
+                                       model._D, model._gamma_f, model._range_f, modulus, truth.data_ptr(),
+                                       candidates.data_ptr() if C else None, cand_ld, C,
+                                       None if nf == 0 else filter_ptr.data_ptr(),
+                                       None if nf == 0 else filter_ids.data_ptr(), nf, ranks.data_ptr(),
+                                       None if ties is None else ties.data_ptr(), None,
+                                       torch.cuda.current_stream(dev).cuda_stream), "kge_eval_rank_candidates")
+    return (ranks, ties) if want_ties else ranks
+
+
+_TIE_RULES = ("optimistic", "pessimistic", "mean")
+
+
+def _transparse_candidates(model, pos, mode, cand, filtered, ties):
+    """TranSparse has no function id: [truth | candidates] scored with model.score, ranked by rank_filtered with the
+    truth in column 0. That composition knows no padding, no filter and no tie count, so it refuses them."""
+    E = model.entity_embedding.shape[0]
+    if filtered or ties != "optimistic" or bool(((cand < 0) | (cand >= E)).any()):
+        raise NotImplementedError("test_step_candidates: TranSparse ranks candidate lists through model.score + "
+                                  "rank_filtered, which takes only lists without padding (every id in [0, nentity)), "
+                                  "no known_triples filter and ties='optimistic'")
+    M = pos.shape[0]
+    col = 0 if mode == "head-batch" else 2
+    rows = cand.unsqueeze(0).expand(M, -1) if cand.dim() == 1 else cand
+    both = torch.cat([pos[:, col:col + 1], rows], dim=1).contiguous()
+    s = model.score(mode, pos, both).detach()
+    if s.shape[1] != both.shape[1]:  # tail-batch scores do not depend on the tail (Q9): one column
+        s = s.expand(M, both.shape[1])
+    return rank_filtered(s.contiguous(), torch.zeros(M, dtype=torch.int64, device=pos.device))
+
+
+def test_step_candidates(model, test_triples, head_candidates, tail_candidates, known_triples=None, batch_size=None,
+                         ties: str = "optimistic"):
+    """Evaluation against given candidate lists (the large-graph protocol: ogbl-wikikg2 ships 500 head and 500 tail
+    negatives per test triple): MRR, MR and HITS@{1,3,10} over the head-batch ranks against `head_candidates` and
+    the tail-batch ranks against `tail_candidates`, each [M, C] (one list per test triple, ragged lists padded with
+    -1) or [C] (one list for all), or None to skip that mode. With `known_triples` (triples, or a FilterTable of
+    them) the other true answers of a query are left out of its list (FilterTable.csr(..., drop_own=True), one call
+    per mode for the whole pass; the batches take views). `ties`: "optimistic" rank = 1 + above (the project's rule;
+    with a shared list of all entities test_step's ranks), "pessimistic" 1 + above + ties, "mean" 1 + above +
+    ties / 2 (the OGB evaluator's rule). Batches of `batch_size` (1 024) queries run through rank_candidates; the
+    ranks stay on the device and go to the host once. TranSparse: model.score + rank_filtered, only for lists
+    without padding, without a filter and with ties="optimistic" (NotImplementedError otherwise)."""
+    if ties not in _TIE_RULES:
+        raise ValueError(f"test_step_candidates: ties must be one of {_TIE_RULES}")
+    bs = int(batch_size or 1024)
+    if bs < 1:
+        raise ValueError("test_step_candidates: batch_size must be positive")
+    ent = model.entity_embedding
+    ops._need_gpu(ent, model.relation_embedding)
+    dev = ent.device
+    triples = np.ascontiguousarray(np.asarray(test_triples, dtype=np.int64).reshape(-1, 3))
+    M = len(triples)
+    lists = {}
+    for mode, c in (("head-batch", head_candidates), ("tail-batch", tail_candidates)):
+        if c is None:
+            continue
+        c = c.to(dev) if torch.is_tensor(c) else torch.from_numpy(np.array(c, dtype=np.int64)).to(dev)
+        if c.dtype != torch.int64 or c.dim() not in (1, 2) or (c.dim() == 2 and c.shape[0] != M):
+            raise ValueError(f"test_step_candidates: the {mode} candidates must be int64, [M, C] or [C]")
+        lists[mode] = c.contiguous()
+    above, tied = [], []
+    with torch.no_grad():
+        if M and lists:
+            pos_all = torch.from_numpy(triples).to(dev)
+            csr = {}
+            if known_triples is not None:
+                table = _device_table(known_triples, dev, "device")
+                for mode in lists:
+                    if table is not None:
+                        ptr_dev, ids_dev, ptr_host = table.csr(pos_all, mode, drop_own=True)
+                    else:  # triples the table build refuses (a negative id): build_filter's CSR, uploaded once
+                        ptr_host, ids = build_filter(triples, mode, known_triples)
+                        ptr_dev, ids_dev = torch.from_numpy(ptr_host).to(dev), torch.from_numpy(ids).to(dev)
+                    csr[mode] = (_batch_ptrs(ptr_dev, M, bs), ids_dev, ptr_host)
+            for mode, cand in lists.items():
+                for s in range(0, M, bs):
+                    n = min(bs, M - s)
+                    pos = pos_all[s:s + n]
+                    c = cand if cand.dim() == 1 else cand[s:s + n]
+                    fptr = fids = None
+                    nf = 0
+                    if mode in csr:
+                        bptr, ids_dev, ph = csr[mode]
+                        nf = int(ph[s + n] - ph[s])
+                        if nf:  # views of the pass's CSR (8-B aligned: the kernel loads the ids one by one)
+                            fptr, fids = bptr[s // bs, :n + 1], ids_dev[int(ph[s]):int(ph[s + n])]
+                    if model.model_name not in FN_IDS:
+                        above.append(_transparse_candidates(model, pos, mode, c, known_triples is not None, ties))
+                        continue
+                    r, t = rank_candidates(model, pos, mode, c, None, fptr, fids, nf, want_ties=True)
+                    above.append(r)
+                    tied.append(t)
+    if not above:
+        return metrics_from_ranks(np.zeros(0, dtype=np.int64))
+    if tied and ties != "optimistic":
+        both = torch.stack([torch.cat(above), torch.cat(tied)]).cpu().numpy()  # the pass's one transfer
+        ranks = both[0] + both[1] if ties == "pessimistic" else both[0] + both[1] / 2.0
+    else:
+        ranks = torch.cat(above).cpu().numpy()
+    return metrics_from_ranks(ranks)
+
+
 TOPK_MAX = 64  # KGE_TOPK_MAX (include/kge_hip.h)
 _TOPK_WS = {}
 
@@ -868,4 +1033,4 @@ def test_step(model, test_triples, all_true_triples, args=None, batch_size=None,
 
 __all__ = ["build_filter", "score_all", "rank_filtered", "rank_planes", "rank_sweep", "RankPipeline", "metrics_from_ranks", "test_step", "entity_planes",
            "split_planes", "HEAD_BATCH", "TAIL_BATCH", "build_exclude", "topk_sweep", "topk_rows", "topk_planes", "predict", "TOPK_MAX",
-           "FilterTable", "build_filter_table"]
+           "FilterTable", "build_filter_table", "rank_candidates", "test_step_candidates"]
