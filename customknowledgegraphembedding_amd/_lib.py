@@ -21,6 +21,7 @@ FN_IDS = {
     "RotatE": 3,
     "InterHT": 4,
     "pRotatE": 5,
+    "PairRE": 7,  # id 6 is unassigned
 }
 # enum kge_mode — the TF reference's integer mode codes (model.py:124,203; supervisor.py:18)
 HEAD_BATCH, TAIL_BATCH, SINGLE = 0, 1, 3

@@ -474,7 +474,33 @@ int check_launch(const char* what) {
 
 bool aligned(const void* ptr, int bytes) { return ptr == nullptr || ((uintptr_t)ptr % (uintptr_t)bytes) == 0; }
 
-bool valid_fn(int fn) { return fn >= KGE_TRANSE && fn <= KGE_PROTATE; }
+// membership, not a range: id 6 is unassigned
+bool valid_fn(int fn) {
+    switch (fn) {
+        case KGE_TRANSE:
+        case KGE_DISTMULT:
+        case KGE_COMPLEX:
+        case KGE_ROTATE:
+        case KGE_INTERHT:
+        case KGE_PROTATE:
+        case KGE_PAIRRE: return true;
+        default: return false;
+    }
+}
+
+// PairRE reads both relation halves, at rel_off and rel_off + D: a row stride that does not hold them is refused
+// (every other function keeps its unchecked strides)
+int check_rel_width(int fn, int64_t D, int64_t rel_off, int64_t rel_ld) {
+    if (fn == KGE_PAIRRE && (rel_off < 0 || rel_ld < rel_off + 2 * D))
+        return fail(KGE_EINVAL, "PairRE relation rows hold two halves: rel_ld >= rel_off + 2 D");
+    return 0;
+}
+
+// the row-sharded family has no PairRE kernels (kKinds' no_pairre): refused ahead of any device call
+int refuse_sharded(int fn, const char* who) {
+    if (fn == KGE_PAIRRE) return fail(KGE_ENOTSUP, std::string(who) + ": PairRE has no row-sharded form");
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------------
 // The problem of a call. Each entry point builds these once from its arguments, in the C-ABI's argument
@@ -556,6 +582,7 @@ int dispatch(int fn, const ScoreParams& p, int kind, hipStream_t st, int blocks,
         case KGE_ROTATE: return launch_rotate(p, kind, st, blocks, ch, V, G);
         case KGE_INTERHT: return launch_interht(p, kind, st, blocks, ch, V, G);
         case KGE_PROTATE: return launch_protate(p, kind, st, blocks, ch, V, G);
+        case KGE_PAIRRE: return launch_pairre(p, kind, st, blocks, ch, V, G);
         default: return KGE_EINVAL;
     }
 }
@@ -576,6 +603,8 @@ int run_score(int fn, int mode, ScoreParams& p, int kind, void* stream) {
     // a rank of the sharded train step that owns no rows has no shard to point at: nothing reads p.cent then
     const bool no_rows =
         p.c_rows == 0 && (kind == KIND_SHARD_FWD_GRAD || kind == KIND_SHARD_POS || kind == KIND_SHARD_EPILOGUE);
+    rc = check_rel_width(fn, p.D, p.r_off, p.r_ld);
+    if (rc) return rc;
     if (!p.qent || !p.rel || (!p.cent && !no_rows)) return fail(KGE_EINVAL, "null table pointer");
     int V = 1, G = 1;
     rc = pick_vg(p, V, G);
@@ -1468,6 +1497,8 @@ int kge_score_sharded(int fn, int mode, const float* qent, int64_t q_ld, const f
                       void* stream) {
     int rc = check_fn_mode(fn, mode);
     if (rc) return rc;
+    rc = refuse_sharded(fn, "kge_score_sharded");
+    if (rc) return rc;
     if (B < 0 || N < 0 || D <= 0 || shard_rows < 0) return fail(KGE_EINVAL, "bad shape");
     if (empty(B, mode == KGE_SINGLE ? 1 : N)) return ok();
     if (!pos || (mode != KGE_SINGLE && !neg) || !scores || !qent || !shard)
@@ -1499,6 +1530,8 @@ int kge_shard_score(int fn, int mode, const float* qent, int64_t q_rows, int64_t
     if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH)
         return fail(KGE_EINVAL, "kge_shard_score: mode must be 0 (head-batch) or 1 (tail-batch)");
     int rc = check_fn_mode(fn, mode);
+    if (rc) return rc;
+    rc = refuse_sharded(fn, "kge_shard_score");
     if (rc) return rc;
     if (B < 0 || N < 0 || D <= 0 || shard_rows <= 0 || q_rows < 0) return fail(KGE_EINVAL, "bad shape");
     if (world < 1 || rank < 0 || rank >= world || home_B <= 0 || B % home_B || home0 < 0 ||
@@ -2080,7 +2113,7 @@ static StepWs step_ws_layout(char* base, int64_t E, int64_t B, int64_t N, int64_
 }
 
 static int64_t ent_width(int fn, int64_t D) { return is_split(fn) ? 2 * D : D; }
-static int64_t rel_width(int fn, int64_t D) { return fn == KGE_COMPLEX ? 2 * D : D; }
+static int64_t rel_width(int fn, int64_t D) { return (fn == KGE_COMPLEX || fn == KGE_PAIRRE) ? 2 * D : D; }
 // Columns of a relation row that belong to the table (the rest of rel_ld is the caller's padding, which no
 // entry point writes): InterHT rows hold three thirds (model.py:209) of which one is read; every other
 // function reads its whole row. Never less than the part read, never more than the row stride.
@@ -2207,6 +2240,8 @@ static int step_backward_impl(const Tables& t, const Batch& b, const StepGrads& 
         return fail(KGE_EINVAL, "null pointer");
     if (B * N + 3 * B >= (int64_t)INT32_MAX || t.nentity >= (int64_t)INT32_MAX)
         return fail(KGE_EINVAL, "too many gradient events for 32-bit codes");
+    rc = check_rel_width(fn, t.D, t.rel_off, t.rel_ld);
+    if (rc) return rc;
     const int64_t ent_w = ent_width(fn, t.D), rel_w = rel_width(fn, t.D);
     // relation rows are written over the table's width (the parts no score function reads get a zero
     // gradient), never over the padding of a row stride wider than the table
@@ -2265,7 +2300,8 @@ static int step_backward_impl(const Tables& t, const Batch& b, const StepGrads& 
         p.dqbuf = w.dqbuf;
         p.dq_scale = g.d_out_neg;
         rc = run_score(fn, mode, p, KIND_BWD_CHAIN, stream);
-    } else if (stream_form(G1) && (fn != KGE_INTERHT || g.cand_stats)) {
+    } else if (stream_form(G1) && kind_has(KIND_BWD_STREAM, fn, false, G1) && (fn != KGE_INTERHT || g.cand_stats)) {
+        // (PairRE has no streaming phase 1: the register-resident form recomputes its candidate norms)
         p.cand_stats = reinterpret_cast<float2*>(const_cast<float*>(g.cand_stats));
         p.dqbuf = w.dqbuf;
         rc = run_score(fn, mode, p, KIND_BWD_STREAM, stream);
@@ -2405,6 +2441,7 @@ int64_t kge_step_backward_adam_workspace_size(int fn, int64_t nentity, int64_t n
                                               int64_t N, int64_t D) {
     const int64_t base = kge_step_backward_workspace_size(fn, nentity, B, N, D);
     if (base < 0 || nrelation < 0 || rel_ld < 0) return -1;
+    if (fn == KGE_PAIRRE && rel_ld < 2 * D) return -1;  // a row stride that cannot hold PairRE's two halves: no step
     return base + align256(nrelation * rel_ld * 4) + 256;
 }
 
@@ -2561,6 +2598,8 @@ static int train_step_impl(int fn, int mode, float* ent, int64_t nentity, int64_
         return fail(KGE_EINVAL, "null pointer");
     if (B * N + 3 * B >= (int64_t)INT32_MAX || nentity >= (int64_t)INT32_MAX)
         return fail(KGE_EINVAL, "too many gradient events for 32-bit codes");
+    rc = check_rel_width(fn, D, rel_off, rel_ld);
+    if (rc) return rc;
     const TrainWs t = train_ws_layout((char*)workspace, fn, nentity, nrelation, rel_ld, B, N, D);
     const RegWs rw = reg_ws_layout((char*)workspace, t.bytes, nentity, nrelation, rel_ld);
     const LazyWs lw = lazy_ws_layout((char*)workspace, rw.bytes, nentity, B, N);
@@ -2772,6 +2811,8 @@ static int shard_check(const Tables& t, const Batch& b, const ShardArgs& a, void
     int rc = check_fn_mode(t.fn, b.mode);
     if (rc) return rc;
     if (t.fn == KGE_PROTATE) return fail(KGE_ENOTSUP, "the sharded train step has no pRotatE modulus gradient");
+    rc = refuse_sharded(t.fn, "the sharded train step");
+    if (rc) return rc;
     if (b.mode == KGE_SINGLE) return fail(KGE_EINVAL, "the sharded train step needs a negative mode (0 or 1)");
     if (b.B <= 0 || b.N <= 0 || t.D <= 0 || t.nentity < 0 || a.world < 1 || a.rank < 0 || a.rank >= a.world ||
         a.home_B <= 0 || a.home_B * a.world != b.B)
@@ -2830,10 +2871,14 @@ static int shard_instance(const ScoreParams& p) {
 
 extern "C" {
 
-int kge_shard_nq(int fn) { return valid_fn(fn) ? shard_nq(fn) : 0; }
+int kge_shard_nq(int fn) {
+    if (refuse_sharded(fn, "kge_shard_nq")) return KGE_ENOTSUP;
+    return valid_fn(fn) ? shard_nq(fn) : 0;
+}
 
 int64_t kge_shard_train_workspace_size(int fn, int64_t shard_rows, int64_t nrelation, int64_t rel_ld, int64_t Bg,
                                        int64_t N, int64_t D) {
+    if (refuse_sharded(fn, "kge_shard_train_workspace_size")) return KGE_ENOTSUP;
     if (!valid_fn(fn) || shard_rows < 0 || nrelation < 0 || rel_ld < 0 || Bg < 0 || N < 0 || D <= 0) return -1;
     return shard_ws_layout(nullptr, fn, shard_rows, nrelation, rel_ld, Bg, N, D).bytes;
 }

@@ -424,6 +424,7 @@ int kge_shard_exec_create(kge_shard_exec** out, kge_comm* comm, int flags, int f
                           void* workspace, int64_t workspace_bytes, int* host_pinned, int64_t host_ints) {
     if (!out) return set_error(KGE_EINVAL, "kge_shard_exec_create: null pointer");
     *out = nullptr;
+    if (fn == KGE_PAIRRE) return set_error(KGE_ENOTSUP, "kge_shard_exec_create: PairRE has no row-sharded form");
     const int64_t need = kge_shard_exec_workspace_size(Bg, N, ent_dim, world, chunks);
     if (need < 0) return (int)need;
     if (rank < 0 || rank >= world || shard_rows <= 0 || D <= 0 || nentity < world)

@@ -216,13 +216,21 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
 }
 
 constexpr bool is_split(int fn) { return fn == KGE_COMPLEX || fn == KGE_ROTATE || fn == KGE_INTERHT; }
-constexpr bool rel_split(int fn) { return fn == KGE_COMPLEX; }
+constexpr bool rel_split(int fn) { return fn == KGE_COMPLEX || fn == KGE_PAIRRE; }
+
+// PairRE's inverse norm of an entity row from its sum of squares: 1 / max(||x||, 1e-12) (F.normalize's clamp), so
+// a zero row normalises to zero and its normalisation is the linear map x 1e12 (norm_clamped: no projection term
+// in its derivative).
+constexpr float kNormInvMax = 1e12f;
+__device__ __forceinline__ float clamped_rsqrt(float s2) { return fminf(rsqrt_f(s2), kNormInvMax); }
+__device__ __forceinline__ bool norm_clamped(float inv) { return inv >= kNormInvMax; }
 
 // ---------------------------------------------------------------------------------------------
 // Query side. CH = candidate is the head (head-batch); otherwise the candidate is the tail
 // (tail-batch and single, which upstream scores with the same "else" branch).
 //   q0,q1,q2: per-element query operands kept in VGPRs; zero on groups past D.
-//   na_inv,nb_inv: InterHT query reciprocal norms (1/||a||, 1/||b||; no epsilon, Q7)
+//   na_inv,nb_inv: InterHT query reciprocal norms (1/||a||, 1/||b||; no epsilon, Q7); PairRE: na_inv alone, the
+//                  query row's clamped one (clamped_rsqrt)
 // ---------------------------------------------------------------------------------------------
 // The hardware v_sin_f32 / v_cos_f32 take their argument in revolutions and are defined for |x| <= 256 of
 // them. hw_sin / hw_cos scale a phase in radians to revolutions and keep only its fraction (v_fract_f32) before
@@ -277,6 +285,13 @@ struct Query {
                 }
             na_inv = rsqrt_f(wave_sum(sa));
             nb_inv = rsqrt_f(wave_sum(sb));
+        } else if constexpr (FN == KGE_PAIRRE) {
+            float sa = 0.f;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+#pragma unroll
+                for (int i = 0; i < V; ++i) sa += ea[k].a[i] * ea[k].a[i];
+            na_inv = clamped_rsqrt(wave_sum(sa));
         }
         // RotatE: the relation phases' cos / sin on the hardware units (hw_cos / hw_sin: two instructions and a
         // fract per element; libm's argument reduction put the query build of the tile kernel's setup and of the
@@ -332,6 +347,12 @@ struct Query {
                     o0 = in ? x * na_inv : 0.f;
                     o1 = in ? (y * nb_inv + 1.f) : 0.f;
                     o2 = r;
+                } else if constexpr (FN == KGE_PAIRRE) {
+                    // the query row normalised, times its side's relation half; the other side's half
+                    // tail: q0 = h^ r_h, q1 = r_t ; head: q0 = t^ r_t, q1 = r_h   (zero past D: zero loads)
+                    const float xh = x * na_inv;
+                    o0 = xh * (CH ? s : r);
+                    o1 = CH ? r : s;
                 }
                 q0[k].a[i] = o0;
                 q1[k].a[i] = o1;
@@ -399,14 +420,32 @@ __device__ __forceinline__ float2 cand_inv_norms(const Cand<FN, V, G>& c) {
             }
         const float ia = rsqrt_f(wave_sum(sa)), ib = rsqrt_f(wave_sum(sb));
         return make_float2(ia, ib);
+    } else if constexpr (FN == KGE_PAIRRE && V % 2 == 0) {  // the whole row's clamped inverse norm, in .x
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        f2 sa2 = {0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int i = 0; i < V; i += 2) {
+                const f2 a{c.ca[k].a[i], c.ca[k].a[i + 1]};
+                sa2 = a * a + sa2;
+            }
+        return make_float2(clamped_rsqrt(wave_sum(sa2.x + sa2.y)), 0.f);
+    } else if constexpr (FN == KGE_PAIRRE) {
+        float sa = 0.f;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int i = 0; i < V; ++i) sa += c.ca[k].a[i] * c.ca[k].a[i];
+        return make_float2(clamped_rsqrt(wave_sum(sa)), 0.f);
     } else {
         return make_float2(0.f, 0.f);
     }
 }
 
 // "Prepare candidate": everything of a candidate's score that no query enters, done in place on its registers.
-// InterHT: the halves normalised (a / ||a||, b / ||b|| + u); pRotatE: the phases (x / phase_div); the other
-// functions: nothing. cand_score_with<.., PREP = true> then scores the prepared row against any number of
+// InterHT: the halves normalised (a / ||a||, b / ||b|| + u); PairRE: the row normalised; pRotatE: the phases
+// (x / phase_div); the other functions: nothing. cand_score_with<.., PREP = true> then scores the prepared row against any number of
 // queries (rank_sweep_kernel: one preparation per candidate row, not one per pair). The expressions are
 // cand_score's own, statement by statement, so both orders round identically (-ffp-contract=on fuses inside a
 // statement only).
@@ -437,6 +476,27 @@ __device__ __forceinline__ void cand_prepare(Cand<FN, V, G>& c, const ScoreParam
                     const float bh = c.cb[k].a[i] * ib + 1.f;
                     c.ca[k].a[i] = ah;
                     c.cb[k].a[i] = bh;
+                }
+        }
+    } else if constexpr (FN == KGE_PAIRRE) {
+        const float ia = cand_inv_norms<FN, V, G>(c).x;
+        if constexpr (V % 2 == 0) {
+            typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+#pragma unroll
+                for (int i = 0; i < V; i += 2) {
+                    const f2 ah = f2{c.ca[k].a[i], c.ca[k].a[i + 1]} * ia;
+                    c.ca[k].a[i] = ah.x;
+                    c.ca[k].a[i + 1] = ah.y;
+                }
+        } else {
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    const float ah = c.ca[k].a[i] * ia;
+                    c.ca[k].a[i] = ah;
                 }
         }
     } else if constexpr (FN == KGE_PROTATE) {
@@ -502,6 +562,44 @@ __device__ __forceinline__ float cand_score_with(const Cand<FN, V, G>& c, float2
                 if (nsg) nsg[k].a[i] = -sgnf(x);  // the Jacobian's sign (0 past D: x = 0 there)
             }
         // groups past D: candidate zero-loaded and query zero -> x = 0
+    } else if constexpr (FN == KGE_PAIRRE && V % 2 == 0) {
+        // InterHT's shape with one normalised row and two operands, on packed fp32 pairs
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        const float ia = inv.x;
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            const vecf<V> q0 = q.q0[k], q1 = q.q1[k];
+#pragma unroll
+            for (int i = 0; i < V; i += 2) {
+                f2 ah = f2{c.ca[k].a[i], c.ca[k].a[i + 1]};
+                if constexpr (!PREP) ah = ah * ia;  // normalised candidate row
+                const f2 Q0{q0.a[i], q0.a[i + 1]}, Q1{q1.a[i], q1.a[i + 1]};
+                // head: h^ r_h - t^ r_t with the candidate the head; tail: the candidate the tail
+                const f2 x = CH ? (ah * Q1 - Q0) : (Q0 - ah * Q1);
+                acc += fabsf(x.x);
+                acc += fabsf(x.y);
+                if (nsg) {  // the Jacobian's sign (0 past D: x = 0 there)
+                    nsg[k].a[i] = -sgnf(x.x);
+                    nsg[k].a[i + 1] = -sgnf(x.y);
+                }
+            }
+        }
+    } else if constexpr (FN == KGE_PAIRRE) {
+        const float ia = inv.x;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                float ah = c.ca[k].a[i];
+                if constexpr (!PREP) ah = ah * ia;  // normalised candidate row
+                float x;
+                if (CH)
+                    x = ah * q.q1[k].a[i] - q.q0[k].a[i];
+                else
+                    x = q.q0[k].a[i] - ah * q.q1[k].a[i];
+                acc += fabsf(x);
+                if (nsg) nsg[k].a[i] = -sgnf(x);  // the Jacobian's sign (0 past D: x = 0 there)
+            }
     } else if constexpr (FN == KGE_ROTATE && V % 2 == 0) {
         // per-element modulus |q - c| on packed fp32 pairs and the hardware v_sqrt_f32 (1 ulp): the IEEE
         // sqrtf expansion (denormal scaling + two Newton corrections, ~15 instructions per element) made the
@@ -554,8 +652,8 @@ template <int FN, bool CH, int V, int G, class Q>
 __device__ __forceinline__ float cand_score(const Cand<FN, V, G>& c, const Q& q, const ScoreParams& p,
                                             float2* stats = nullptr, vecf<V>* nsg = nullptr) {
     const float2 inv = cand_inv_norms<FN, V, G>(c);
-    if constexpr (FN == KGE_INTERHT) {
-        if (stats) *stats = inv;  // kept for the streaming phase-1 backward
+    if constexpr (FN == KGE_INTERHT || FN == KGE_PAIRRE) {
+        if (stats) *stats = inv;  // kept for the streaming phase-1 backward (InterHT) and the fused query pass
     }
     return cand_score_with<FN, CH, V, G, false>(c, inv, q, p, nsg);
 }
@@ -2160,10 +2258,10 @@ __device__ __forceinline__ void rot_unit(float xr, float xi, float& fr, float& f
 // 5 waves per SIMD to 2), and pRotatE is outside the fused query pass anyway.
 // An ElemGrad is bound to one column group's query operands; the candidate's halves come per element, as
 // halves() gives them (cand_grad, which needs InterHT's b / |b| by itself, normalises on its own).
-//   residual   the quantity whose modulus the score sums: InterHT x, TransE r, RotatE (xr, xi)
+//   residual   the quantity whose modulus the score sums: InterHT / PairRE x, TransE r, RotatE (xr, xi)
 //   at         what all directions of the element share, under the weight w: G = w d score / d residual
 //   dq         d score / d (q0, q1, q2), term k = c[k] f[k] with c = +-G: a caller adds c f in one expression
-//   dc         d score / d (the candidate's halves; InterHT: the normalised ones), weighted
+//   dc         d score / d (the candidate's halves; InterHT / PairRE: the normalised ones), weighted
 // Rounding (-ffp-contract=on fuses per source expression): a product with a sign (+-1, 0) is exact, so the weight
 // may sit on either side of it. The weight is an argument, so that a caller with one weight folds it into the sign
 // first (w sgn, then times the factor, as its code always did) and the two-weight caller passes 1.
@@ -2174,8 +2272,9 @@ struct ElemGrad {
     const bool in;  // the group lies inside the row
     const ScoreParams& p;
     static_assert(FN != KGE_PROTATE, "pRotatE's callers keep their own expressions");
-    static constexpr int kNQ = FN == KGE_INTERHT ? 3 : ((FN == KGE_COMPLEX || FN == KGE_ROTATE) ? 2 : 1);
-    static constexpr bool kPairs = FN == KGE_INTERHT && V % 2 == 0;  // jac_pairs exists
+    static constexpr int kNQ =
+        FN == KGE_INTERHT ? 3 : ((FN == KGE_COMPLEX || FN == KGE_ROTATE || FN == KGE_PAIRRE) ? 2 : 1);
+    static constexpr bool kPairs = (FN == KGE_INTERHT || FN == KGE_PAIRRE) && V % 2 == 0;  // jac_pairs exists
     struct At {
         float G, ur, ui;  // ur, ui: RotatE's rot_unit of the residual
     };
@@ -2185,6 +2284,9 @@ struct ElemGrad {
         if constexpr (FN == KGE_INTERHT) {
             a = ca.a[i] * ia;
             b = cb.a[i] * ib + 1.f;
+        } else if constexpr (FN == KGE_PAIRRE) {
+            a = ca.a[i] * ia;
+            b = 0.f;
         } else {
             a = ca.a[i];
             b = cb.a[i];
@@ -2196,6 +2298,8 @@ struct ElemGrad {
     __device__ __forceinline__ T residual(T a, T b, T Q0, T Q1, T Q2, T& xi) const {
         if constexpr (FN == KGE_INTERHT) {
             return CH ? (a * Q1 - Q0 * b + Q2) : (Q0 * b - a * Q1 + Q2);
+        } else if constexpr (FN == KGE_PAIRRE) {
+            return CH ? (a * Q1 - Q0) : (Q0 - a * Q1);
         } else if constexpr (FN == KGE_TRANSE) {
             return CH ? (a + Q0) : (Q0 - a);
         } else if constexpr (FN == KGE_ROTATE) {
@@ -2210,7 +2314,7 @@ struct ElemGrad {
     __device__ __forceinline__ At at(int i, float a, float b, float w, const vecf<V>* nsg = nullptr) const {
         At t{w, 0.f, 0.f};
         float xi;
-        if constexpr (FN == KGE_INTERHT) {
+        if constexpr (FN == KGE_INTERHT || FN == KGE_PAIRRE) {
             t.G = nsg ? w * nsg->a[i] : (in ? -w * sgnf(residual(a, b, q0.a[i], q1.a[i], q2.a[i], xi)) : 0.f);
         } else if constexpr (FN == KGE_TRANSE) {
             t.G = -w * sgnf(residual(a, b, q0.a[i], q1.a[i], q2.a[i], xi));
@@ -2235,6 +2339,10 @@ struct ElemGrad {
             f[0] = b;
             f[1] = a;
             f[2] = one;
+        } else if constexpr (FN == KGE_PAIRRE) {  // tail: x = q0 - a q1; head: x = a q1 - q0
+            c[CH ? 0 : 1] = -G;
+            f[0] = one;
+            f[1] = a;
         } else if constexpr (FN == KGE_ROTATE) {
             f[0] = ur;
             f[1] = ui;
@@ -2253,6 +2361,8 @@ struct ElemGrad {
         if constexpr (FN == KGE_INTERHT) {
             da = (CH ? t.G : -t.G) * q1.a[i];
             db = (CH ? -t.G : t.G) * q0.a[i];
+        } else if constexpr (FN == KGE_PAIRRE) {
+            da = (CH ? t.G : -t.G) * q1.a[i];
         } else if constexpr (FN == KGE_TRANSE) {
             da = CH ? t.G : -t.G;
         } else if constexpr (FN == KGE_DISTMULT) {
@@ -2275,7 +2385,7 @@ struct ElemGrad {
         if constexpr (kNQ > 2) d2 += c[2] * f[2];
     }
 
-    // InterHT's Jacobian sums on packed fp32 pairs (v_pk_mul / v_pk_fma_f32: two elements per instruction), a
+    // InterHT's (and PairRE's: one normalised row, no third operand) Jacobian sums on packed fp32 pairs (v_pk_mul / v_pk_fma_f32: two elements per instruction), a
     // measured optimisation of the fused forward: the sign by sgn2, and the sums take nwa = -wa and nwb = -wb so
     // that nwa sgn(x) = wa G. No range mask: past D the candidate, q0, q1 and q2 are 0, so x = 0 and the element
     // adds nothing.
@@ -2283,11 +2393,12 @@ struct ElemGrad {
     __device__ __forceinline__ void jac_pairs(const vecf<V>& ca, const vecf<V>& cb, float ia, float ib, float nwa,
                                               float nwb, vecf<V>& a0, vecf<V>& a1, vecf<V>& a2, vecf<V>& b0,
                                               vecf<V>& b1, vecf<V>& b2) const {
-        static_assert(kPairs, "InterHT at an even width");
+        static_assert(kPairs, "InterHT or PairRE at an even width");
 #pragma unroll
         for (int i = 0; i < V; i += 2) {
             const f32x2 ah = f32x2{ca.a[i], ca.a[i + 1]} * ia;
-            const f32x2 bh = f32x2{cb.a[i], cb.a[i + 1]} * ib + 1.f;
+            f32x2 bh = {0.f, 0.f};
+            if constexpr (FN == KGE_INTERHT) bh = f32x2{cb.a[i], cb.a[i + 1]} * ib + 1.f;
             const f32x2 Q0{q0.a[i], q0.a[i + 1]}, Q1{q1.a[i], q1.a[i + 1]}, Q2{q2.a[i], q2.a[i + 1]};
             f32x2 xi;
             const f32x2 sg = sgn2(residual(ah, bh, Q0, Q1, Q2, xi));
@@ -2297,7 +2408,7 @@ struct ElemGrad {
                 f32x2 u0{s0.a[i], s0.a[i + 1]}, u1{s1.a[i], s1.a[i + 1]}, u2{s2.a[i], s2.a[i + 1]};
                 u0 = u0 + c[0] * f[0];
                 u1 = u1 + c[1] * f[1];
-                u2 = u2 + c[2] * f[2];
+                if constexpr (kNQ > 2) u2 = u2 + c[2] * f[2];
                 s0.a[i] = u0.x;
                 s0.a[i + 1] = u0.y;
                 s1.a[i] = u1.x;
@@ -2631,6 +2742,42 @@ __device__ __forceinline__ void cand_grad(const Cand<FN, V, G>& c, const Query<F
                     dcb[k].a[i] = (dcb[k].a[i] - bn * dotb) * ib;
                 }
         }
+    } else if constexpr (FN == KGE_PAIRRE) {  // InterHT's a-half code on the whole row
+        float sa = 0.f;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int i = 0; i < V; ++i) sa += c.ca[k].a[i] * c.ca[k].a[i];
+        const float ia = clamped_rsqrt(wave_sum(sa));
+        float dota = 0.f;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const float ah = c.ca[k].a[i] * ia;
+                const ElemGrad<FN, CH, V> e{q.q0[k], q.q1[k], q.q2[k], (lane + k * kWave) < DV, p};
+                const auto t = e.at(i, ah, 0.f, g);
+                if (ACC_Q) e.add_dq(t, ah, 0.f, dq0[k].a[i], dq1[k].a[i], dq2[k].a[i]);
+                if (WANT_C) {
+                    float dah, dbn = 0.f;
+                    e.dc(t, i, dah, dbn);
+                    dca[k].a[i] = dah;
+                    dota += ah * dah;
+                }
+            }
+        if constexpr (WANT_C) {
+            // d(x/n) = (dy - y <y, dy>) / n; the clamped (linear) form x 1e12 has no projection term
+            dota = wave_sum(dota);
+            if (norm_clamped(ia)) dota = 0.f;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    const float ah = c.ca[k].a[i] * ia;
+                    dca[k].a[i] = (dca[k].a[i] - ah * dota) * ia;
+                    dcb[k].a[i] = 0.f;
+                }
+        }
     } else if constexpr (FN == KGE_PROTATE) {  // not an ElemGrad caller: see there
         float ysum = 0.f;
 #pragma unroll
@@ -2695,6 +2842,16 @@ __device__ __forceinline__ void query_chain(const Query<FN, CH, V, G>& q, const 
             }
         dna = wave_sum(da);
         dnb = wave_sum(db);
+    } else if constexpr (FN == KGE_PAIRRE) {
+        // <e^, d e^> with d e^ = dq0 o (the side's relation half) and q0 = e^ o that half: sum q0 dq0; the clamped
+        // (linear) normalisation has no projection term
+        float da = 0.f;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int i = 0; i < V; ++i) da += q.q0[k].a[i] * dq0[k].a[i];
+        dna = wave_sum(da);
+        if (norm_clamped(q.na_inv)) dna = 0.f;
     }
     const uint32_t qb = qok ? (uint32_t)D * 4u : 0u, rbytes = rok ? (uint32_t)D * 4u : 0u;
     const rsrc_t sqa = make_rsrc(qrow, qb), sqb = make_rsrc(qrow + D, is_split(FN) ? qb : 0u);
@@ -2751,6 +2908,14 @@ __device__ __forceinline__ void query_chain(const Query<FN, CH, V, G>& q, const 
                 o_ea = (d0 - Q0 * dna) * q.na_inv;
                 o_eb = (d1 - bn * dnb) * q.nb_inv;
                 o_ra = d2;
+            } else if constexpr (FN == KGE_PAIRRE) {
+                // q0 = e^ o rs (rs: the query side's relation half), q1 = the other half: both halves get gradient
+                const float xh = x * q.na_inv;
+                const float rs = CH ? s : r;
+                o_ea = (d0 * rs - xh * dna) * q.na_inv;
+                const float o_rs = d0 * xh;
+                o_ra = CH ? d1 : o_rs;
+                o_rb = CH ? o_rs : d1;
             }
             gea[k].a[i] = in ? o_ea : 0.f;
             geb[k].a[i] = in ? o_eb : 0.f;
@@ -3554,7 +3719,9 @@ constexpr int kEntSortMax = 2048;
 
 // query operands a candidate event of function FN reads from the slot's stored query (InterHT's third,
 // the relation row, is read from the relation table instead: it stays in L2)
-constexpr int ent_nq(int fn) { return (fn == KGE_COMPLEX || fn == KGE_ROTATE || fn == KGE_INTERHT) ? 2 : 1; }
+constexpr int ent_nq(int fn) {
+    return (fn == KGE_COMPLEX || fn == KGE_ROTATE || fn == KGE_INTERHT || fn == KGE_PAIRRE) ? 2 : 1;
+}
 
 template <int FN, bool CH, int V, int G, bool REG = false, bool LAZY = false>  // REG, LAZY: as bwd_ent_kernel's
 __global__ __launch_bounds__(kBlock) void bwd_ent_stream_kernel(ScoreParams p) {
@@ -3629,7 +3796,7 @@ __global__ __launch_bounds__(kBlock) void bwd_ent_stream_kernel(ScoreParams p) {
     float ia = 0.f, ib = 0.f;
     bool any_cand = false;
     if (n > 0) {
-        // InterHT's half-norms of the row (block-wide; every wave calls this at the same point)
+        // InterHT's half-norms / PairRE's norm of the row (block-wide; every wave calls this at the same point)
         auto norms = [&]() {
             if constexpr (FN == KGE_INTERHT) {
                 float s2a = 0.f, s2b = 0.f;
@@ -3643,6 +3810,13 @@ __global__ __launch_bounds__(kBlock) void bwd_ent_stream_kernel(ScoreParams p) {
                 const float2 s = block_sum2(s2a, s2b, red, lane, w);
                 ia = rsqrt_f(s.x);
                 ib = rsqrt_f(s.y);
+            } else if constexpr (FN == KGE_PAIRRE) {  // the whole row's clamped inverse norm
+                float s2a = 0.f;
+#pragma unroll
+                for (int gg = 0; gg < GW; ++gg)
+#pragma unroll
+                    for (int i = 0; i < V; ++i) s2a += ca[gg].a[i] * ca[gg].a[i];
+                ia = clamped_rsqrt(block_sum2(s2a, 0.f, red, lane, w).x);
             }
         };
         // one event: its slice of the slot's stored query (candidate event) or of the slot's
@@ -3791,6 +3965,20 @@ __global__ __launch_bounds__(kBlock) void bwd_ent_stream_kernel(ScoreParams p) {
                         sa[gg].a[i] = (sa[gg].a[i] - (ca[gg].a[i] * ia) * dot.x) * ia;
                         sb[gg].a[i] = (sb[gg].a[i] - (cb[gg].a[i] * ib) * dot.y) * ib;
                     }
+            }
+        } else if constexpr (FN == KGE_PAIRRE) {
+            if (any_cand) {  // block-uniform, as above
+                float da = 0.f;
+#pragma unroll
+                for (int gg = 0; gg < GW; ++gg)
+#pragma unroll
+                    for (int i = 0; i < V; ++i) da += (ca[gg].a[i] * ia) * sa[gg].a[i];
+                float dot = block_sum2(da, 0.f, red, lane, w).x;
+                if (norm_clamped(ia)) dot = 0.f;  // the clamped (linear) form has no projection term
+#pragma unroll
+                for (int gg = 0; gg < GW; ++gg)
+#pragma unroll
+                    for (int i = 0; i < V; ++i) sa[gg].a[i] = (sa[gg].a[i] - (ca[gg].a[i] * ia) * dot) * ia;
             }
         }
 #pragma unroll

@@ -102,7 +102,9 @@ struct KindInfo {
     bool no_protate;    // the fused forward + query gradient family: no pRotatE modulus gradient
     bool interht_only;  // keeps InterHT's candidate norms
     const char* what;   // check_launch's name for the launch
-    bool distance_only = false;  // TransE, RotatE, pRotatE, InterHT (DistMult / ComplEx rank through the planes)
+    bool distance_only = false;  // TransE, RotatE, pRotatE, InterHT, PairRE (DistMult / ComplEx rank through the planes)
+    bool no_pairre = false;      // the row-sharded family, and the streaming phase 1 (which takes the candidates'
+                                 // norms from the forward's InterHT-only stats): no PairRE instance
 };
 constexpr KindInfo kKinds[KIND_COUNT] = {
     /* KIND_FWD */             {GRID_CAND_PER_WAVE, true, kMaxG, false, false, false, "kge score launch"},
@@ -110,7 +112,7 @@ constexpr KindInfo kKinds[KIND_COUNT] = {
     /* KIND_FINISH */          {GRID_WAVE_PER_ROW, false, kMaxG, false, false, false, "kge finish launch"},
     /* KIND_BWD_ROWS */        {GRID_BLOCK_PER_ROW, true, kMaxG, false, false, false, "kge score launch"},
     /* KIND_BWD_ENT */         {GRID_WAVE_PER_ENT, true, kMaxG, false, false, false, "kge score launch"},
-    /* KIND_BWD_STREAM */      {GRID_BLOCK_PER_ROW, true, kMaxG, true, false, false, "kge score launch"},
+    /* KIND_BWD_STREAM */      {GRID_BLOCK_PER_ROW, true, kMaxG, true, false, false, "kge score launch", false, true},
     /* KIND_BWD_CHAIN */       {GRID_WAVE_PER_ROW, true, kMaxG, false, false, false, "kge score launch"},
     /* KIND_FWD_STATS */       {GRID_CAND_PER_WAVE, true, kMaxG, false, false, true, "kge score launch"},
     /* KIND_STEP_FWD */        {GRID_BLOCK_PER_ROW, true, kMaxG, false, false, false, "kge score launch"},
@@ -118,12 +120,12 @@ constexpr KindInfo kKinds[KIND_COUNT] = {
     /* KIND_BWD_ENT_STREAM */  {GRID_BLOCK_PER_ENT, true, kMaxG, true, false, false, "kge score launch"},
     /* KIND_STEP_FWD_GRAD */   {GRID_BLOCK_PER_ROW, true, kFwdGradMaxG, false, true, false, "kge score launch"},
     /* KIND_STEP_EPILOGUE */   {GRID_STEP_EPILOGUE, true, kFwdGradMaxG, false, true, false, "kge score launch"},
-    /* KIND_SHARD_FWD_GRAD */  {GRID_BLOCK_PER_ROW, true, kFwdGradMaxG, false, true, false, "kge score launch"},
-    /* KIND_SHARD_POS */       {GRID_WAVE_PER_ROW, false, kFwdGradMaxG, false, true, false, "kge score launch"},
-    /* KIND_SHARD_EPILOGUE */  {GRID_SHARD_EPILOGUE, true, kFwdGradMaxG, false, true, false, "kge score launch"},
+    /* KIND_SHARD_FWD_GRAD */  {GRID_BLOCK_PER_ROW, true, kFwdGradMaxG, false, true, false, "kge score launch", false, true},
+    /* KIND_SHARD_POS */       {GRID_WAVE_PER_ROW, false, kFwdGradMaxG, false, true, false, "kge score launch", false, true},
+    /* KIND_SHARD_EPILOGUE */  {GRID_SHARD_EPILOGUE, true, kFwdGradMaxG, false, true, false, "kge score launch", false, true},
     /* KIND_STEP_FWD_XCD */    {GRID_XCD_SLICES, true, kMaxG, false, false, false, "kge score launch"},
     /* KIND_SCORE_SHARD_XCD */ {GRID_XCD_SLICES, true, kMaxG, false, false, false, "kge score launch"},
-    /* KIND_SHARD_BUCKET */    {GRID_XCD_SLICES, true, kMaxG, false, false, false, "kge score launch"},
+    /* KIND_SHARD_BUCKET */    {GRID_XCD_SLICES, true, kMaxG, false, false, false, "kge score launch", false, true},
     /* KIND_STEP_FWD_TILE */   {GRID_TILE_GROUPS, true, kFwdGradMaxG, false, false, false, "kge score launch"},
     /* KIND_SCORE_TILE */      {GRID_TILE_GROUPS, true, kFwdGradMaxG, false, false, false, "kge score launch"},
     /* KIND_RANK_PAIRS */      {GRID_RANK_PAIRS, true, kSweepMaxG, false, false, false, "kge_eval_rank_sweep", true},
@@ -136,7 +138,7 @@ constexpr bool kind_has(int k, int fn, bool ch, int G) {
     return G <= kKinds[k].max_g && (!kKinds[k].g_whole_waves || G % kWavesPerBlock == 0) &&
            (!kKinds[k].distance_only || (fn != KGE_DISTMULT && fn != KGE_COMPLEX)) &&
            (!kKinds[k].no_protate || fn != KGE_PROTATE) && (!kKinds[k].interht_only || fn == KGE_INTERHT) &&
-           (kKinds[k].ch || !ch);
+           (!kKinds[k].no_pairre || fn != KGE_PAIRRE) && (kKinds[k].ch || !ch);
 }
 constexpr int kTileBuckets = 256;  // entity buckets of a slice (the block's counting sort)
 constexpr int kTileRows = 16;     // rows per block the library takes when they fit (tile_plan)
@@ -146,11 +148,16 @@ constexpr int kTileMaxRows = 20;
 constexpr int kTileLdsMax = 160 * 1024;
 constexpr int kTileSortRel = 64;     // relation buckets of the tile kernel's row sort (ids >= 62 share one)
 constexpr int kTileSortMaxB = 2048;  // batch rows the tile kernel sorts by relation in LDS
-// LDS query operands per batch row of the tile kernel (InterHT's third, the relation, is read per candidate)
-constexpr int tile_nq(int fn) { return (fn == KGE_COMPLEX || fn == KGE_ROTATE || fn == KGE_INTERHT) ? 2 : 1; }
-// query operands a score function's gradient has (q0 always; q1 for the complex / split forms; q2 InterHT)
+// LDS query operands per batch row of the tile kernel (InterHT's third, the relation, is read per candidate;
+// PairRE's second is the other side's relation half)
+constexpr int tile_nq(int fn) {
+    return (fn == KGE_COMPLEX || fn == KGE_ROTATE || fn == KGE_INTERHT || fn == KGE_PAIRRE) ? 2 : 1;
+}
+// query operands a score function's gradient has (q0 always; q1 for the complex / split forms and PairRE; q2
+// InterHT): the operand images of the rank / top-k sweeps and the row-sharded step's gradient width (which has
+// no PairRE: kKinds' no_pairre)
 constexpr int shard_nq(int fn) {
-    return fn == KGE_INTERHT ? 3 : ((fn == KGE_COMPLEX || fn == KGE_ROTATE) ? 2 : 1);
+    return fn == KGE_INTERHT ? 3 : ((fn == KGE_COMPLEX || fn == KGE_ROTATE || fn == KGE_PAIRRE) ? 2 : 1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -388,6 +395,7 @@ int launch_complex(const ScoreParams& p, int kind, hipStream_t st, int blocks, b
 int launch_rotate(const ScoreParams& p, int kind, hipStream_t st, int blocks, bool ch, int V, int G);
 int launch_interht(const ScoreParams& p, int kind, hipStream_t st, int blocks, bool ch, int V, int G);
 int launch_protate(const ScoreParams& p, int kind, hipStream_t st, int blocks, bool ch, int V, int G);
+int launch_pairre(const ScoreParams& p, int kind, hipStream_t st, int blocks, bool ch, int V, int G);
 
 // link-prediction evaluation (kge_eval.hip)
 int launch_eval_query_any(int fn, bool ch, const ScoreParams& p, hipStream_t st, int blocks, int V, int G, float* Q,

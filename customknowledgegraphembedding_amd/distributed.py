@@ -699,6 +699,8 @@ class ShardedKGE:
         # communicator was given and `exchange` is set: tests run the whole collective path under RCCL on one GPU
         self.exchange = self.world > 1
         self.kernels = kernels or HipShardKernels()
+        if model_name == "PairRE":
+            raise NotImplementedError("PairRE has no row-sharded form (the kge_shard_* family answers KGE_ENOTSUP)")
         self.model_name = model_name
         self.fn = FN_IDS[model_name]
         self.nentity = nentity

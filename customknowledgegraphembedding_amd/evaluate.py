@@ -221,7 +221,7 @@ def rank_planes(model, positive_sample: torch.Tensor, mode: str, planes: torch.T
     return ranks
 
 
-SWEEP_FNS = ("TransE", "RotatE", "pRotatE", "InterHT")
+SWEEP_FNS = ("TransE", "RotatE", "pRotatE", "InterHT", "PairRE")
 _SWEEP_WS = {}
 _ENOTSUP = -95  # KGE_ENOTSUP (include/kge_hip.h)
 
@@ -722,7 +722,7 @@ def topk_planes(model, positive_sample: torch.Tensor, mode: str, k: int, planes:
 # The functions predict sends through topk_sweep: those whose sweep measured faster than score_all + topk_rows by
 # DESIGN §3.0's rule (§3.4, profiles/r11_topk_ab.txt); the others, and every batch topk_sweep answers None for, take
 # the matrix path.
-TOPK_SWEEP_FNS = ("TransE", "RotatE", "pRotatE", "InterHT")
+TOPK_SWEEP_FNS = ("TransE", "RotatE", "pRotatE", "InterHT", "PairRE")
 # The functions predict sends through topk_planes, up to TOPK_PLANES_MAX_K, by the same rule (§3.4,
 # profiles/r15_topk_planes_ab.txt). Empty: the selecting epilogue has not measured faster than score_all +
 # topk_rows; topk_planes is there for callers short of the [B, E] matrix's memory.

@@ -45,6 +45,12 @@ def _dims_for(model_name, entity_dim, relation_dim):
         if entity_dim % 2 or relation_dim % 3 or entity_dim // 2 != relation_dim // 3:
             raise ValueError("InterHT needs -de and -tr (entity 2d, relation 3d)")
         return entity_dim // 2, entity_dim // 2
+    if model_name == "PairRE":
+        # upstream PairRE: the relation row holds (r_h | r_t), each as wide as the unsplit entity row
+        if relation_dim != 2 * entity_dim:
+            raise ValueError(f"PairRE needs relation_dim == 2 * entity_dim (-dr, no -de), got {entity_dim} / "
+                             f"{relation_dim}")
+        return entity_dim, 0
     if model_name == "TranSparse":
         # model.py:227: head [.., d] @ (mask * W)[d, d] and the relation row of width d
         if entity_dim != relation_dim:
@@ -203,12 +209,12 @@ class TFKGEModel(_KGEBase):
         self.embedding_range = nn.Parameter(rng.clone(), requires_grad=False)
 
         # model.py:65-78 — Q5: the -dr result is overwritten by the -tr branch, so -dr is dead.
-        # ComplEx cannot be built at all without a double relation, so there (only) -dr is honoured.
+        # ComplEx and PairRE cannot be built at all without a double relation, so there (only) -dr is honoured.
         relation_dim = hidden_dim * 2 if double_relation_embedding else hidden_dim
         entity_dim = hidden_dim * 2 if double_entity_embedding else hidden_dim
         if triple_relation_embedding:
             relation_dim = hidden_dim * 3
-        elif not (model_name == "ComplEx" and double_relation_embedding):
+        elif not (model_name in ("ComplEx", "PairRE") and double_relation_embedding):
             relation_dim = hidden_dim
         self.entity_dim, self.relation_dim = entity_dim, relation_dim
 
@@ -397,8 +403,10 @@ class KGEModel(_KGEBase):
             torch.Tensor([(self.gamma.item() + self.epsilon) / hidden_dim]), requires_grad=False)
         self.entity_dim = hidden_dim * 2 if double_entity_embedding else hidden_dim
         self.relation_dim = hidden_dim * 2 if double_relation_embedding else hidden_dim
-        if model_name not in ("TransE", "DistMult", "ComplEx", "RotatE", "pRotatE", "InterHT"):
+        if model_name not in ("TransE", "DistMult", "ComplEx", "RotatE", "pRotatE", "InterHT", "PairRE"):
             raise ValueError("model %s not supported" % model_name)
+        if model_name == "PairRE" and (double_entity_embedding or not double_relation_embedding):
+            raise ValueError("PairRE should use --double_relation_embedding")
         if model_name == "RotatE" and (not double_entity_embedding or double_relation_embedding):
             raise ValueError("RotatE should use --double_entity_embedding")
         if model_name == "ComplEx" and (not double_entity_embedding or not double_relation_embedding):

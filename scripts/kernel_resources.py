@@ -18,7 +18,7 @@ import argparse
 import re
 import sys
 
-FN_NAMES = {0: "TransE", 1: "DistMult", 2: "ComplEx", 3: "RotatE", 4: "InterHT", 5: "pRotatE"}
+FN_NAMES = {0: "TransE", 1: "DistMult", 2: "ComplEx", 3: "RotatE", 4: "InterHT", 5: "pRotatE", 7: "PairRE"}
 
 
 def parse(path):
